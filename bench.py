@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: MonoDETR training img/s on KITTI-shaped 1280x384 synthetic images.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,13 +10,20 @@ included), backward, AdamW update -- ResNet-50 MonoDETR, per-GPU batch 16, fp32 
 precision), inputs resident in HBM before the timed region.  N > 1: one process per GPU, DDP over
 RCCL, per-GPU work fixed ("weak" scaling), value = all images of all ranks / max-over-ranks time.
 
-One JSON line on rank 0 (contract in the task description) with two extra objects:
+One JSON line on rank 0: metric, value (img/s), unit, higher_is_better, dtype, ms_per_step (one timed
+step), steps, warmup, config.  A plain run sets up, warms up, times the K steps and prints that line;
+--dump-outputs DIR also writes what the last timed step computed (dump_outputs below; that step starts
+from the initial state, see step_state).  --full adds
+every other measurement, each in objects of its own:
   roofline      -- the dominant MSDA kernel: algorithmic bytes per launch / average
-                   launch duration measured here with HIP events on the launch stream / 8 TB/s
+                   launch duration measured here with HIP events on the launch stream / 8 TB/s;
+                   roofline.step (counted dense FLOPs), roofline.trained_offsets (operator probe)
+  inference, dataloader -- the eval-mode forward and the DataLoader-fed train step, timed like the headline
   cpu_baseline  -- the CPU restatement (oracle grid_sample formulation, "port") timed on this host,
                    bounded sample (N=1, rank 0 only)
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -28,6 +35,9 @@ if ROOT not in sys.path:
 
 HBM_PEAK_BYTES_PER_S = 8.0e12      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 F32_MATRIX_PEAK_FLOPS = 157.3e12   # MI355X_MICROARCH.md: FP32 vector / matrix peak (v_mfma_f32_32x32x2_f32: the exact-f32 path the step computes in)
+DUMP_BUDGET_BYTES = 64 << 20       # --dump-outputs: all files together
+DUMP_MAX_FULL = 1 << 21            # --dump-outputs: larger arrays are written as a sample of DUMP_SAMPLE elements
+DUMP_SAMPLE = 1 << 20
 
 
 def log(msg):
@@ -76,7 +86,18 @@ def parse():
     ap.add_argument("--no-offsets-probe", action="store_true", help="skip the trained-offsets MSDA probe (roofline.trained_offsets)")
     ap.add_argument("--no-miopen-db", action="store_true",
                     help="ignore the shipped MIOpen find results (monosowa_amd/miopen_db) and use MIOpen's heuristics")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline: per-kernel MSDA roofline, roofline.step, trained-offsets probe, "
+                         "DataLoader-fed and inference legs, CPU baseline (each --no-* option above still drops its leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB: arrays above %d elements as a fixed seeded sample)" % DUMP_MAX_FULL)
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline and nothing else: it is repeated for every change
+        args.no_cpu_baseline = args.no_inference_leg = args.no_dataloader_leg = True
+        args.no_step_roofline = args.no_offsets_probe = True
+    return args
 
 
 def msda_alg_bytes(kind, dims):
@@ -137,11 +158,12 @@ def build_everything(args, device):
 _PROBE_SLEEP = float(os.environ.get("MONOSOWA_PROBE_SLEEP_MS", "0")) * 1e-3     # host-slack probe (tools only)
 
 
-def train_step_fn(model, criterion, optimizer, accum=1):
+def train_step_fn(model, criterion, optimizer, accum=1, keep=None):
     """One optimizer step.  accum > 1: that many micro-steps over the same resident batch with gradient accumulation (each
     micro-batch's losses scaled by 1 / accum; under DDP the all-reduce runs once, with the last micro-step) -- the
     fixed-global-batch definition of a step.  The criterion normalises every micro-batch by its own box count, as the reference
-    loop would when it accumulates (trainer_helper.py:123-150 has no accumulation of its own)."""
+    loop would when it accumulates (trainer_helper.py:123-150 has no accumulation of its own).  ``keep``: a dict that receives
+    the last micro-step's model outputs and losses (--dump-outputs)."""
     import contextlib
     from monosowa_amd.monodetr.criterion import weighted_total
     from monosowa_amd.synthetic import prepare_targets
@@ -161,6 +183,8 @@ def train_step_fn(model, criterion, optimizer, accum=1):
                     time.sleep(_PROBE_SLEEP)
                 (total if accum == 1 else total / accum).backward()
         optimizer.step()
+        if keep is not None:
+            keep.update(loss=total, losses=loss_dict, outputs=outputs)
         return total
     return step
 
@@ -421,11 +445,14 @@ def barrier_sync(device):
         torch.cuda.synchronize()
 
 
-def timed_steps(step, batch, steps, device):
-    """EXACTLY `steps` steps between two barrier_sync()s; returns the max-over-ranks seconds."""
+def timed_steps(step, batch, steps, device, before_last=None):
+    """EXACTLY `steps` steps between two barrier_sync()s; returns the max-over-ranks seconds.  ``before_last``: called right
+    before the last step (--dump-outputs: the state restore that makes the last step's inputs the same in every run)."""
     barrier_sync(device)
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for i in range(steps):
+        if before_last is not None and i == steps - 1:
+            before_last()
         step(batch)
     barrier_sync(device)
     return max_over_ranks(time.perf_counter() - t0, device)
@@ -439,6 +466,87 @@ def preheat(step, batch, seconds, device, sync):
         sync()
         n += 1
     return n, time.time() - t1
+
+
+def step_state(model, optimizer, device):
+    """Snapshot, taken before the first step, of everything a step reads besides the batch and changes: parameters, buffers,
+    the torch RNGs and the dropout seed counters of the HIP kernels.  Returns ``restore()``, which puts them back in place (same
+    storage: the fused AdamW plan keeps parameter addresses) and sets the optimizer's state to what a fresh optimizer starts
+    from (moments zero, step 0) -- a few multi-tensor launches, no host synchronisation.  The model and batch come from fixed
+    seeds, so after a restore every run computes the same next step (up to the float atomics' summation order)."""
+    import torch
+    from monosowa_amd import flash_attn, pointwise
+    tensors = list(model.parameters()) + list(model.buffers())
+    saved = [t.detach().clone() for t in tensors]
+    rng = (torch.get_rng_state(), torch.cuda.get_rng_state(device) if device.type == "cuda" else None)
+    counters = flash_attn._seed_counter[0], pointwise._seed_counter[0]
+
+    def restore():
+        with torch.no_grad():
+            torch._foreach_copy_([t.data for t in tensors], saved)
+            moments = []
+            for st in optimizer.state.values():
+                for k, v in st.items():
+                    if torch.is_tensor(v):
+                        moments.append(v)
+                    else:
+                        st[k] = 0
+            if moments:
+                torch._foreach_zero_(moments)
+        torch.set_rng_state(rng[0])
+        if rng[1] is not None:
+            torch.cuda.set_rng_state(rng[1], device)
+        flash_attn._seed_counter[0], pointwise._seed_counter[0] = counters
+    return restore
+
+
+def _flat_tensors(obj, prefix):
+    """(name, tensor) for every tensor in nested dicts / lists / tuples, names joined with '.'."""
+    import torch
+    if torch.is_tensor(obj):
+        yield prefix, obj
+    elif isinstance(obj, dict):
+        for k in obj:
+            yield from _flat_tensors(obj[k], "%s.%s" % (prefix, k))
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            yield from _flat_tensors(v, "%s.%d" % (prefix, i))
+
+
+def dump_outputs(directory, keep, model, train):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy.  Train mode: the total loss, every loss term, the
+    model outputs and, after the AdamW update, the parameters and their gradients (all parameters flattened in
+    named_parameters() order and concatenated; a missing gradient counts as zeros).  Inference: the model outputs.  float64
+    stays float64, everything else is written as float32 (integers and flags as float64).  An array of more than DUMP_MAX_FULL
+    elements is written as DUMP_SAMPLE elements at fixed seeded positions (``<name>.sample``), the same in every run."""
+    import zlib
+    import numpy as np
+    import torch
+    arrays = list(_flat_tensors(keep.get("outputs"), "outputs"))
+    if train:
+        arrays = [("loss", keep["loss"])] + list(_flat_tensors(dict(keep["losses"]), "losses")) + arrays
+        net = model.module if hasattr(model, "module") else model
+        params = [p for _, p in net.named_parameters()]
+        with torch.no_grad():
+            arrays.append(("params", torch.cat([p.detach().reshape(-1) for p in params])))
+            arrays.append(("grads", torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1)
+                                               for p in params])))
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, t in arrays:
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 or not t.is_floating_point() else t.float()
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_MAX_FULL:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t, name = flat[idx.to(flat.device)], name + ".sample"
+        a = t.cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_BUDGET_BYTES:
+            raise SystemExit("--dump-outputs: more than %d MB" % (DUMP_BUDGET_BYTES >> 20))
+        np.save(os.path.join(directory, name + ".npy"), a)
+    log("dump: %d arrays, %.1f MB in %s" % (len(arrays), total / 2 ** 20, directory))
 
 
 _TRACE = os.environ.get("MONOSOWA_BENCH_TRACE") == "1" or os.environ.get("MONOSOWA_BENCH_REHEARSAL") == "1"
@@ -545,32 +653,47 @@ def main():
         assert train and args.global_batch % (args.batch * world) == 0, "--global-batch must be a multiple of gpus * batch"
         accum = args.global_batch // (args.batch * world)
 
+    keep = {} if args.dump_outputs and rank == 0 else None        # --dump-outputs: the last step's results
     if train:
-        step0 = train_step_fn(model, criterion, optimizer, accum)
+        step0 = train_step_fn(model, criterion, optimizer, accum, keep)
     elif not args.graph:
         def step0(b):
             with torch.no_grad():
-                return model(b[0], b[1], None, b[2]["img_size"])["pred_logits"]
+                out = model(b[0], b[1], None, b[2]["img_size"])
+            if keep is not None:
+                keep["outputs"] = out
+            return out["pred_logits"]
     else:
         from monosowa_amd.helpers.tester_helper import GraphedForward
         assert resample is None, "--graph replays a captured forward of the resident batch"
         graphed = GraphedForward(model, batch[0], batch[1], batch[2]["img_size"])
 
         def step0(b):
-            return graphed(b[0], b[1], b[2]["img_size"])["pred_logits"]
+            out = graphed(b[0], b[1], b[2]["img_size"])
+            if keep is not None:
+                keep["outputs"] = out
+            return out["pred_logits"]
     step = step0 if resample is None else (lambda b: step0(resample(b)))
 
     def sync():
         barrier_sync(device)
 
     log("model + batch ready; warm-up")
+    restore = step_state(model, optimizer, device)
     if args.preheat_seconds > 0:
         trace("first step: enter")
         step(batch)                       # first step: library initialisation, MIOpen kernel selection
         torch.cuda.synchronize()
         trace("first step: done")
         n, dt = preheat(step, batch, args.preheat_seconds, device, torch.cuda.synchronize)
+        restore()                         # the warm-up starts from the initial state, however long the pre-heat ran
+        torch.cuda.synchronize()
         log("pre-heat: %d untimed steps in %.1f s (not counted as warm-up steps)" % (n, dt))
+    # --dump-outputs (train): the last timed step starts from the initial state again, so that what it computes is the same in
+    # every run; without it, W + K - 1 earlier steps would each add their atomics' rounding and AdamW would amplify it
+    before_last = restore if args.dump_outputs and train else None
+    if before_last is None:
+        del restore
     for i in range(args.warmup):
         t1 = time.time()
         step(batch)
@@ -578,8 +701,10 @@ def main():
         log("warm-up step %d: %.2f s" % (i, time.time() - t1))
         trace("warm-up step %d done" % i)
 
-    with MSDA.LaunchTimer() as timer:
-        elapsed = timed_steps(step, batch, args.steps, device)
+    # per-launch HIP events on the MSDA calls (the roofline object): --full only
+    timer = MSDA.LaunchTimer() if args.full else None
+    with timer or contextlib.nullcontext():
+        elapsed = timed_steps(step, batch, args.steps, device, before_last)
     log("timed %d steps: %.3f s" % (args.steps, elapsed))
     trace("timed region done")
 
@@ -587,6 +712,8 @@ def main():
     matcher = getattr(criterion, "matcher", None)
     if train and matcher is not None and hasattr(matcher, "check_device_status"):
         matcher.check_device_status(block=True)
+    if keep is not None:
+        dump_outputs(args.dump_outputs, keep, model, train)
 
     global_batch = args.batch * world * accum
     value = global_batch * args.steps / elapsed
@@ -638,7 +765,7 @@ def main():
         log("inference leg: %d eval steps in %.3f s" % (args.inference_steps, i_elapsed))
 
     kernels = []
-    for (kind, dims), d in sorted(timer.summary().items(), key=lambda kv: -kv[1]["total_ms"]):
+    for (kind, dims), d in sorted(timer.summary().items() if timer else (), key=lambda kv: -kv[1]["total_ms"]):
         ab = msda_alg_bytes(kind, dims)
         ach = ab / (d["avg_ms"] * 1e-3)
         kernels.append({"kernel": "msda_%s" % kind, "Lq": dims[5], "B": dims[0], "launches_per_step": d["launches"] / args.steps,

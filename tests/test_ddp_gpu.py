@@ -363,7 +363,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu_prints_the_contract_line():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--preheat-seconds", "2",
-           "--inference-steps", "2"]
+           "--inference-steps", "2", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -31,6 +31,19 @@ def _rel(a, b):
     return (a - b).abs().max().item() / max(b.abs().max().item(), 1e-30)
 
 
+def _cpu_reproduces_fixture_bits(golden_dir):
+    """The CPU halves of the AdamW and decode fixtures hold what torch's CPU kernels computed on the machine that made them.  Two
+    elementary functions there, sqrt and exp, come from MKL's vector math, whose last bit depends on the code path MKL picks for
+    the processor (on that machine MKL_ENABLE_INSTRUCTIONS=AVX2 alone changes it; an AMD EPYC gets other bits again).
+    cpu_elementary.npz holds that machine's torch.sqrt / torch.exp of seeded inputs: where this CPU reproduces them the fixtures
+    are compared bit for bit, elsewhere this CPU is another device and the cross-device comparisons of the GPU tests apply."""
+    g = _npz(golden_dir, "cpu_elementary")
+    rng = np.random.default_rng(0)
+    x = torch.from_numpy(rng.uniform(1e-3, 4.0, 16384).astype(np.float32))
+    y = torch.from_numpy((rng.standard_normal(16384) * 4).astype(np.float32))
+    return np.array_equal(torch.sqrt(x).numpy(), g["sqrt"]) and np.array_equal(torch.exp(y).numpy(), g["exp"])
+
+
 # ------------------------------------------------------------------------------------------------ AdamW
 def _adamw_case(g, device):
     from monosowa_amd.helpers.optimizer_helper import AdamW
@@ -60,6 +73,10 @@ def _adamw_case(g, device):
 
 def test_adamw_cpu_equals_reference_class(golden_dir):
     g = _npz(golden_dir, "adamw")
+    if not _cpu_reproduces_fixture_bits(golden_dir):
+        worst = _adamw_case(g, "cpu")            # sqrt differs in the last bit: the HIP kernel test's tolerance
+        assert worst <= 1.0, worst
+        return
     from monosowa_amd.helpers.optimizer_helper import AdamW
     n, steps = int(g["n_params"]), int(g["n_steps"])
     params = [torch.nn.Parameter(torch.from_numpy(g["p%d_init" % i])) for i in range(n)]
@@ -88,7 +105,7 @@ def test_adamw_hip_kernel_equals_reference_class(golden_dir):
 
 
 # ------------------------------------------------------------------------------------------------ decode
-def _decode_case(g, device):
+def _decode_case(g, device, exact=False):
     from monosowa_amd.helpers.decode_helper import PinholeCalib, decode_detections, extract_dets_from_outputs
     outputs = {k: torch.from_numpy(g[k]).to(device) for k in ("pred_logits", "pred_boxes", "pred_3d_dim", "pred_depth", "pred_angle")}
     dets = extract_dets_from_outputs(outputs, K=50, topk=50).cpu()
@@ -97,7 +114,7 @@ def _decode_case(g, device):
     assert torch.equal(dets[:, :, 0], want[:, :, 0])                     # class ids = topk_indexes % C, exact
     # everything else is a gather of the inputs (exact) or sigmoid / exp / box arithmetic (1 ulp on another device)
     gathered = [6] + list(range(7, 31)) + list(range(31, 34)) + [34, 35]
-    if device == "cpu":
+    if exact:
         assert torch.equal(dets, want)
     else:
         # torch.topk orders exact score ties differently on another device (unspecified in the reference too, whose own
@@ -124,7 +141,7 @@ def _decode_case(g, device):
 
 
 def test_decode_equals_reference_functions(golden_dir):
-    _decode_case(_npz(golden_dir, "decode"), "cpu")
+    _decode_case(_npz(golden_dir, "decode"), "cpu", exact=_cpu_reproduces_fixture_bits(golden_dir))
 
 
 @pytest.mark.gpu
