@@ -49,6 +49,11 @@ int mono_gemm_nn_f32(const float *dY, long long lddy, const float *W, long long 
  * timing (no synchronisation, e.g. under stream capture).  Default 32 (66.50 -> 66.33 ms per train step against 8, round 5).  Returns the previous value. */
 int mono_gemm_set_autotune(int n);
 
+/* Deterministic mode (torch.use_deterministic_algorithms): on != 0 selects without timing -- the library's first choice, the same
+ * kernel in every process on the same build and device type -- and keys the selection cache by the mode, so that kernels timed
+ * before the switch are not reused under it.  Returns the previous value (0 | 1). */
+int mono_gemm_set_deterministic(int on);
+
 /* Number of (shape, epilogue) keys selected so far (tests / diagnostics). */
 int mono_gemm_cache_size(void);
 

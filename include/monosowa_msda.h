@@ -58,7 +58,7 @@
 extern "C" {
 #endif
 
-#define MSDA_ABI_VERSION 10
+#define MSDA_ABI_VERSION 11
 
 #define MSDA_E_NULLPTR (-1)   /* a required pointer is NULL                        */
 #define MSDA_E_SHAPE (-2)     /* a dimension is <= 0 or exceeds the indexing range */
@@ -71,7 +71,15 @@ const char *msda_strerror(int code);
 /* Kernel-generation switches for A/B measurements and tests (process-wide; not thread-safe against
  * concurrent launches).  "gather": 0 | 1 | 2 (default 2), "scatter_fixed": 0 | 1 (default 1),
  * "scatter_sorted": 0 | 1 | 2 (default 0; 1: the sort-then-sum scatter on long record lists, 2: always).  Every setting
- * computes the same function.  Returns 0, or MSDA_E_UNSUPPORTED for an unknown name / value. */
+ * computes the same function.  Returns 0, or MSDA_E_UNSUPPORTED for an unknown name / value.
+ * ABI v11: "deterministic": 0 (default) | 1.  On, the f32 backward with D = 32, L = P = 4 (plain, fused and view entry points)
+ * is bitwise reproducible: every f32 addition into a gradient runs in an order fixed by the inputs and the geometry.  It
+ * overrides the switches that select arrival-order sums (scatter_rows, scatter_bands, scatter_sorted, scatter_fixed = 0,
+ * scatter_lists): grad_value comes from the record-list scatter with 64-bit fixed-point tile sums, each tile owned by one
+ * workgroup.  msda_fused_save_supported*() answer 0 and msda_saved_plan_f32() MSDA_E_UNSUPPORTED while it is on (the saved
+ * tensors are laid out for the row-tile scatter).  The workspace size is the default mode's.  The f64 and generic (D != 32,
+ * L * P != 16) backward kernels add with float atomics in any mode: callers that promise reproducibility refuse them.  The
+ * forward is deterministic in every mode. */
 int msda_set_option(const char *name, int value);
 
 /* A hash of the option table entries a plan made by msda_saved_plan_f32() depends on: a caller that keeps such a plan across other

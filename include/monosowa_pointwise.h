@@ -11,6 +11,13 @@
 extern "C" {
 #endif
 
+/* Deterministic mode (torch.use_deterministic_algorithms), process-wide, read at every launch: on != 0 makes the GroupNorm
+ * statistics and the head tail's depth-map gradient -- the two entry points below that add in arrival order (f64 / f32
+ * atomics) -- add in a fixed order instead: per-workgroup partial rows summed in workgroup order, and the map gradient summed
+ * in query order in LDS (maps of at most 12288 cells, else -3).  Every other kernel of this library is deterministic in any
+ * mode.  Returns the previous value (0 | 1). */
+int mono_set_deterministic(int on);
+
 /* y[r, c] = act(y[r, c] + bias[c] (+ residual[r, c])) in place; residual may be NULL; relu != 0 applies max(., 0). */
 int mono_bias_act_f32(float *y, const float *bias, const float *residual, long long rows, int C, int relu, void *stream);
 /* The frozen stem (reference backbone.py:72-74, 83; torchvision's ResNet stem): out = max_pool2d(relu(y + bias), 3, stride 2, padding 1)
@@ -156,6 +163,12 @@ int mono_groupnorm_nhwc_fwd_f32(const float *x, const float *pre_bias, const flo
 /* Workgroups of the backward = rows (of 256 floats) of gbias_partials it needs. */
 int mono_groupnorm_blocks(int B, int HW);
 
+/* Doubles the forward's `stats` / the backward's `part` must hold: B * 64 / B * 512 (the layouts below), plus, while the
+ * deterministic mode is on, a slab of per-workgroup partial sums behind them (mono_groupnorm_blocks(B, HW) rows of 64 / 512).
+ * That mode stores every element, so the buffers then need not be zero on entry. */
+long long mono_groupnorm_stats_doubles(int B, int HW);
+long long mono_groupnorm_part_doubles(int B, int HW);
+
 /* gx [B, HW, 256].  part: f64 [B, 256, 2], ZERO on entry; on return part[b][c] = {sum gy'*xhat, sum gy'} so that
  * ggamma[c] = sum_b part[b][c][0], gbeta[c] = sum_b part[b][c][1].  y = forward output (ReLU mask), NULL if relu == 0.
  * With pre_bias != NULL: gbias [256] = gradient of pre_bias, gbias_partials = scratch.
@@ -221,7 +234,8 @@ int mono_lsap_match_flat_f32(const float *cost, int NL, int B, int Q, int T, int
 /* Per-level tail of MonoDETR's detection heads (monodetr.py:238-263), one launch each way: coords [B, Q, 6] = sigmoid(tmp),
  * depth_ave [B, Q, 2] = ((1 / (sigmoid(depth_reg0) + 1e-6) - 1 + size3d0 / max((coords4 + coords5) img_h, 1) fu
  *                        + bilinear(wdepth [B, H, W]; coords0, coords1 -- F.grid_sample, align_corners, zero padding)) / 3, depth_reg1).
- * backward: g_coords / g_depth_ave may be NULL (no gradient); g_wdepth [B, H, W] must be ZERO on entry (atomics); the sampling
+ * backward: g_coords / g_depth_ave may be NULL (no gradient); g_wdepth [B, H, W] must be ZERO on entry (atomics; in deterministic mode
+ * it is overwritten, and H * W > 12288 returns -3); the sampling
  * location carries no gradient through the depth map (detached in the reference). */
 int mono_head_tail_fwd_f32(const float *tmp, const float *size3d, const float *depth_reg, const float *wdepth, const float *fu,
                            const float *img_h, float *coords, float *depth_ave, int B, int Q, int H, int W, const float *ref,

@@ -159,6 +159,10 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
     B, S, M, D, L, Lq, P = _dims(value, spatial_shapes, sampling_loc, attn_weight)
     _assert(grad_output.numel() == B * Lq * M * D and grad_output.dtype == value.dtype, "grad_output shape/dtype mismatch")
     lib = _lib.load()
+    if _lib.MSDA_DETERMINISTIC.sync() and not (value.dtype == torch.float32 and D == 32 and L == 4 and P == 4 and M * L * 8 <= 1024):
+        # (the f64 and generic kernels add grad_value with float atomics in arrival order)
+        _lib.alert_not_deterministic("ms_deform_attn_backward", "the %s backward with D = %d, L = %d, P = %d adds grad_value with "
+                                     "float atomics" % (str(value.dtype).replace("torch.", ""), D, L, P))
     if Lq == 0:        # no query: nothing is added to the reference's zero-initialised gradients (cu:121-123)
         return [torch.zeros_like(value), torch.zeros_like(sampling_loc), torch.zeros_like(attn_weight)]
     grad_value = torch.empty_like(value)
@@ -235,6 +239,7 @@ def ms_deform_attn_fused_backward(value, spatial_shapes, level_start_index, samp
     B, S, M, D, L, Lq, P = _fused_dims(value, sampling_offsets, attention_logits, reference_points)
     _assert(grad_output.is_contiguous() and grad_output.numel() == B * Lq * M * D, "grad_output shape mismatch")
     lib = _lib.load()
+    _lib.MSDA_DETERMINISTIC.sync()
     geom = host_geometry(spatial_shapes, level_start_index)
     grad_value = torch.empty_like(value)
     grad_off = torch.empty_like(sampling_offsets)
@@ -328,6 +333,7 @@ def plan_saved_backward(value, spatial_shapes, level_start_index, loc):
     L = P = 4
     Lq = loc.shape[3]
     lib = _lib.load()
+    _lib.MSDA_DETERMINISTIC.sync()
     geom = host_geometry(spatial_shapes, level_start_index)
     ws_bytes = lib.msda_backward_workspace_bytes(B, S, M, D, L, Lq, P, 4)
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=value.device)
@@ -354,6 +360,11 @@ def _fused_backward_view(value, spatial_shapes, level_start_index, a, b, saved, 
     Lq = a.shape[3] if saved else a.shape[1]
     _assert(grad_output.is_contiguous() and grad_output.numel() == B * Lq * M * D, "grad_output shape mismatch")
     lib = _lib.load()
+    if _lib.MSDA_DETERMINISTIC.sync() and saved:
+        # the saved tensors are laid out for the row-tile scatter, which has no deterministic variant (the mode was switched on
+        # between this call's forward and its backward: fused_save_supported() answers False while it is on)
+        _lib.alert_not_deterministic(name, "the saved-prologue backward runs the row-tile scatter")
+        _lib.MSDA_DETERMINISTIC.force(False)               # (warn_only: run it as it is)
     geom = host_geometry(spatial_shapes, level_start_index)
     ts, mask_ptr, mask = _value_view(value, value_mask)
     grad_value = torch.empty((B, S, M, D), dtype=value.dtype, device=value.device)         # always dense
@@ -414,6 +425,7 @@ def fused_save_supported(value, spatial_shapes, level_start_index, Lq, ref_dim=2
     the self-attention shape (Lq == S) on the window / row-tile kernels."""
     B, S, M, D = value.shape
     geom = host_geometry(spatial_shapes, level_start_index)
+    _lib.MSDA_DETERMINISTIC.sync()                           # (deterministic mode: never -- the backward re-evaluates the prologue)
     # ``value`` may be a column block of a wider projection: its token stride bounds the kernels' plane addressing too
     return bool(_lib.load().msda_fused_save_supported_view(S, M, D, 4, Lq, 4, ref_dim, value.stride(1), M * 48, M * 48,
                                                            geom[0], geom[1]))

@@ -14,7 +14,7 @@ SYMBOLS = ("msda_abi_version", "msda_strerror", "msda_set_option", "msda_options
            "msda_fused_backward_saved_f32")
 
 _lib = None
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class MSDALibraryError(RuntimeError):
@@ -96,6 +96,55 @@ def debug_counter(name):
     out = ctypes.c_ulonglong(0)
     check(load().msda_debug_counter(name.encode(), ctypes.byref(out)), "msda_debug_counter(%s)" % name)
     return int(out.value)
+
+
+class DeterministicSwitch:
+    """Mirrors ``torch.are_deterministic_algorithms_enabled()`` into one native library's process-wide switch: ``sync()`` reads
+    torch's flag on every call and calls ``setter(0 | 1)`` only when it differs from the value last set (a switch set behind
+    its back, e.g. by a test through the C ABI, is not tracked)."""
+
+    def __init__(self, setter):
+        self._setter = setter
+        self._on = False
+
+    def sync(self):
+        import torch
+        on = torch.are_deterministic_algorithms_enabled()
+        if on != self._on:
+            self.force(on)
+        return on
+
+    def force(self, on):
+        """Sets the native switch regardless of torch's flag, until the next ``sync()``."""
+        self._setter(int(on))
+        self._on = bool(on)
+
+
+_ALERTED = set()
+
+
+def alert_not_deterministic(op, reason):
+    """PyTorch's convention for an operation without a deterministic implementation while
+    ``torch.use_deterministic_algorithms(True)`` is in force: ``RuntimeError`` naming the op and the reason, or, under
+    ``warn_only=True``, a ``UserWarning`` once per op (and the op runs).  Nothing when the mode is off."""
+    import torch
+    if not torch.are_deterministic_algorithms_enabled():
+        return
+    msg = ("%s does not have a deterministic implementation (%s), but you set 'torch.use_deterministic_algorithms(True)'"
+           % (op, reason))
+    if not torch.is_deterministic_algorithms_warn_only_enabled():
+        raise RuntimeError(msg)
+    if op not in _ALERTED:
+        _ALERTED.add(op)
+        import warnings
+        warnings.warn(msg, stacklevel=3)
+
+
+def _set_msda_deterministic(on):
+    check(load().msda_set_option(b"deterministic", on), "msda_set_option(deterministic, %d)" % on)
+
+
+MSDA_DETERMINISTIC = DeterministicSwitch(_set_msda_deterministic)
 
 
 def raw_stream():

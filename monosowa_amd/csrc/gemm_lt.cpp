@@ -29,6 +29,7 @@ struct DeviceState {
 std::mutex g_mutex;
 std::map<int, DeviceState> g_devices;
 int g_autotune = 32;
+int g_deterministic = 0;          // 1: no timing, the heuristic's first candidate (mono_gemm_set_deterministic)
 
 // (kind, m, n, k, lda, ldb, ldc, ldd, flags) in the library's column-major terms
 typedef std::tuple<int, int, int, int, long long, long long, long long, long long, int> Key;
@@ -111,7 +112,8 @@ int run(const Problem &p, hipStream_t stream) {
     LT_CHECK(hipblasLtMatrixLayoutCreate(&lc, HIP_R_32F, p.m, p.n, p.ldc));
     LT_CHECK(hipblasLtMatrixLayoutCreate(&ld, HIP_R_32F, p.m, p.n, p.ldd));
 
-    const int flags = (int)p.epilogue * 4 + (p.alpha_vec ? 1 : 0) + (p.beta != 0.f ? 2 : 0);
+    // the mode is part of the key: a deterministic call never reuses a kernel another process might not have timed to
+    const int flags = (int)p.epilogue * 4 + (p.alpha_vec ? 1 : 0) + (p.beta != 0.f ? 2 : 0) + (g_deterministic ? 1 << 30 : 0);
     const auto key = std::make_pair(dev, Key(p.kind, p.m, p.n, p.k, p.lda, p.ldb, p.ldc, p.ldd, flags));
     auto it = g_algos.find(key);
     if (it == g_algos.end()) {
@@ -119,7 +121,7 @@ int run(const Problem &p, hipStream_t stream) {
       const uint64_t ws = kWorkspaceBytes;
       LT_CHECK(hipblasLtMatmulPreferenceSetAttribute(pref, HIPBLASLT_MATMUL_PREF_MAX_WORKSPACE_BYTES, &ws, sizeof(ws)));
       const bool aliased = p.beta != 0.f && (const float *)p.d == p.c;       // repeated launches would accumulate: no timing
-      const int want = (g_autotune > 1 && !aliased) ? g_autotune : 1;
+      const int want = (g_autotune > 1 && !aliased && !g_deterministic) ? g_autotune : 1;
       std::vector<hipblasLtMatmulHeuristicResult_t> res(want);
       int got = 0;
       LT_CHECK(hipblasLtMatmulAlgoGetHeuristic(ds.handle, desc, la, lb, lc, ld, pref, want, res.data(), &got));
@@ -243,6 +245,13 @@ int mono_gemm_set_autotune(int n) {
   std::lock_guard<std::mutex> lock(g_mutex);
   const int prev = g_autotune;
   g_autotune = n;
+  return prev;
+}
+
+int mono_gemm_set_deterministic(int on) {
+  std::lock_guard<std::mutex> lock(g_mutex);
+  const int prev = g_deterministic;
+  g_deterministic = on != 0;
   return prev;
 }
 

@@ -11,6 +11,9 @@
 //   backward: gn_bwd_stats_kernel -> part[b][c] = {sum gy' * xhat, sum gy'}   (gy' = gy masked by the ReLU)
 //             gn_bwd_apply_kernel -> gx = rstd * (gy' * gamma - (sum_g gy' gamma + xhat * sum_g gy' gamma xhat) / n)
 // ggamma / gbeta are the sums of part over b: by one wave of gn_bwd_apply_kernel's first workgroup (ggamma_gbeta [2][256]), or by the caller.
+// Deterministic mode (DET = true, mono_set_deterministic): the two statistics kernels store each workgroup's partial sums into a
+// slab behind the [B, ...] result instead of adding them with f64 atomics in arrival order, and gn_fold_kernel adds the slab's
+// rows in workgroup order (mono_groupnorm_stats_doubles / mono_groupnorm_part_doubles size the buffers).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +34,7 @@ __device__ __forceinline__ float4 load_bias(const float *pre_bias, int lane) {
   return pre_bias ? reinterpret_cast<const float4 *>(pre_bias)[lane] : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+template <bool DET = false>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float *__restrict__ x, const float *__restrict__ pre_bias,
                                                        double *__restrict__ stats, int HW) {
   __shared__ double red[4][kGnG][2];
@@ -54,7 +58,10 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float *__restrict__
   if (threadIdx.x < 64) {
     const int g = threadIdx.x >> 1, k = threadIdx.x & 1;
     const double t = (red[0][g][k] + red[1][g][k]) + (red[2][g][k] + red[3][g][k]);
-    atomicAdd(stats + ((long long)b * kGnG + g) * 2 + k, t);
+    if constexpr (DET)   // slab [B][gridDim.x][32][2] behind stats [B][32][2]
+      stats[(long long)gridDim.y * kGnG * 2 + (((long long)b * gridDim.x + blockIdx.x) * kGnG + g) * 2 + k] = t;
+    else
+      atomicAdd(stats + ((long long)b * kGnG + g) * 2 + k, t);
   }
 }
 
@@ -88,7 +95,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float *__restrict__
 }
 
 // y is the saved forward output when RELU (its sign is the ReLU mask), unused otherwise.
-template <bool RELU>
+template <bool RELU, bool DET = false>
 __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const float *__restrict__ gy, const float *__restrict__ x,
                                                            const float *__restrict__ pre_bias, const float *__restrict__ y,
                                                            const float *__restrict__ mean_rstd, double *__restrict__ part, int HW) {
@@ -120,10 +127,26 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const float *__restri
   }
   __syncthreads();
   if (!wave) {
-    double *dst = part + ((long long)b * kGnC + lane * 4) * 2;
+    if constexpr (DET) {   // slab [B][gridDim.x][256][2] behind part [B][256][2]
+      double *dst = part + (long long)gridDim.y * kGnC * 2 + (((long long)b * gridDim.x + blockIdx.x) * kGnC + lane * 4) * 2;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) atomicAdd(dst + k, a[k] + (red[0][lane][k] + red[1][lane][k]) + red[2][lane][k]);
+      for (int k = 0; k < 8; ++k) dst[k] = a[k] + (red[0][lane][k] + red[1][lane][k]) + red[2][lane][k];
+    } else {
+      double *dst = part + ((long long)b * kGnC + lane * 4) * 2;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) atomicAdd(dst + k, a[k] + (red[0][lane][k] + red[1][lane][k]) + red[2][lane][k]);
+    }
   }
+}
+
+// DET: out[b][i] = sum over the slab rows of image b, in workgroup order (slab = out + B * width); one workgroup per image.
+__global__ __launch_bounds__(512) void gn_fold_kernel(double *__restrict__ out, int n_blocks, int width) {
+  const int b = blockIdx.x, i = threadIdx.x;
+  if (i >= width) return;
+  const double *slab = out + (long long)gridDim.x * width + (long long)b * n_blocks * width + i;
+  double s = 0.0;
+  for (int k = 0; k < n_blocks; ++k) s += slab[(long long)k * width];
+  out[(long long)b * width + i] = s;
 }
 
 // gbias_partials (with pre_bias): one row of 256 per workgroup = sum of gx over the workgroup's pixels (the bias gradient

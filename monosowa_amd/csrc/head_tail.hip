@@ -76,7 +76,8 @@ __global__ __launch_bounds__(256) void head_tail_fwd_kernel(const HeadTailArgs a
   depth_ave[i * 2 + 1] = a.depth_reg[i * 2 + 1];
 }
 
-// g_wdepth must be ZERO on entry.
+// g_wdepth must be ZERO on entry.  DET: g_wdepth is left alone (head_tail_wdepth_kernel writes it).
+template <bool DET = false>
 __global__ __launch_bounds__(256) void head_tail_bwd_kernel(const HeadTailArgs a, const float *__restrict__ g_coords,
                                                             const float *__restrict__ g_dave, float *__restrict__ g_tmp,
                                                             float *__restrict__ g_size3d, float *__restrict__ g_dreg,
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256) void head_tail_bwd_kernel(const HeadTailArgs a
   const float s = sigmoidf_(a.depth_reg[i * 2]), se = s + 1e-6f;
   g_dreg[i * 2] = g0 * (-1.f / (se * se)) * (s * (1.f - s));
   g_dreg[i * 2 + 1] = g1;
-  if (g0 != 0.f) {
+  if (!DET && g0 != 0.f) {
     const HeadTap t = head_tap(oc[0], oc[1], a.H, a.W);
     float *m = g_wdepth + (long long)b * a.H * a.W + t.y0 * a.W + t.x0;
     if (t.nw) atomicAdd(m, g0 * t.wnw);
@@ -108,6 +109,48 @@ __global__ __launch_bounds__(256) void head_tail_bwd_kernel(const HeadTailArgs a
   }
 #pragma unroll
   for (int k = 0; k < 6; ++k) g_tmp[i * 6 + k] = goc[k] * (oc[k] * (1.f - oc[k]));
+}
+
+// Deterministic mode (mono_set_deterministic): the depth-map gradient of head_tail_bwd_kernel without atomics.  One workgroup
+// per image holds its map in LDS; the threads evaluate 256 queries' corner weights at a time, then ONE wave adds them in query
+// order (lane c: corner c -- a query's four corners are distinct cells), so every cell's sum runs in the same order on every
+// run.  The map is stored whole: g_wdepth need not be zero.  Maps of more than kHeadMapCap cells are refused by the caller.
+constexpr int kHeadMapCap = 12288;   // 48 KB of LDS (the shipped map: 48 x 160)
+__global__ __launch_bounds__(256) void head_tail_wdepth_kernel(const HeadTailArgs a, const float *__restrict__ g_dave,
+                                                               float *__restrict__ g_wdepth) {
+  __shared__ float map[kHeadMapCap];
+  __shared__ int cell[256][4];
+  __shared__ float wt[256][4];
+  const int b = blockIdx.x, n_cells = a.H * a.W;
+  for (int i = threadIdx.x; i < n_cells; i += 256) map[i] = 0.f;
+  for (int q0 = 0; q0 < a.Q; q0 += 256) {
+    const int q = q0 + threadIdx.x;
+    int c4[4] = {-1, -1, -1, -1};
+    float w4[4] = {0.f, 0.f, 0.f, 0.f};
+    const float g0 = (g_dave && q < a.Q) ? g_dave[((long long)b * a.Q + q) * 2] / 3.f : 0.f;
+    if (g0 != 0.f) {                              // the same products head_tail_bwd_kernel adds
+      const int i = b * a.Q + q;
+      const HeadTap t = head_tap(sigmoidf_(head_logit(a, i, 0)), sigmoidf_(head_logit(a, i, 1)), a.H, a.W);
+      const int c = t.y0 * a.W + t.x0;
+      if (t.nw) { c4[0] = c; w4[0] = g0 * t.wnw; }
+      if (t.ne) { c4[1] = c + 1; w4[1] = g0 * t.wne; }
+      if (t.sw) { c4[2] = c + a.W; w4[2] = g0 * t.wsw; }
+      if (t.se) { c4[3] = c + a.W + 1; w4[3] = g0 * t.wse; }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { cell[threadIdx.x][k] = c4[k]; wt[threadIdx.x][k] = w4[k]; }
+    __syncthreads();                              // (also orders the zero fill)
+    if (threadIdx.x < 4) {                        // one wave, in query order: LDS accesses of a wave complete in issue order
+      const int n = min(256, a.Q - q0), k = threadIdx.x;
+      for (int j = 0; j < n; ++j) {
+        const int c = cell[j][k];
+        if (c >= 0) map[c] += wt[j][k];
+      }
+    }
+    __syncthreads();
+  }
+  float *dst = g_wdepth + (long long)b * n_cells;
+  for (int i = threadIdx.x; i < n_cells; i += 256) dst[i] = map[i];
 }
 
 // The decoder's iterative reference refinement (depthaware_transformer.py:602-613), detached in the reference:

@@ -71,6 +71,10 @@ struct Options {
   int scatter_bands = 1;       // 1 (default): row-band scatter (msda_backward_bands.hip) for short record lists (Lq <= 576: the decoder)
   int plan_fused = 1;          // 1 (default): statistics + per-head plan + candidate tables in one launch (plan_fused_kernel); 0: three kernels
   int plan_reach = 8;          // capacity of the directional scan: |footprint - centre| beyond this many pixels is "far" in any case
+  int deterministic = 0;       // 1: bitwise-reproducible f32 backward (torch.use_deterministic_algorithms): overrides the options above
+                               // that select a path whose sums run in arrival order -- the row-tile scatter and its far-point atomics,
+                               // the band and sorted scatters, the f64 tile accumulators -- for the record-list scatter with 64-bit
+                               // fixed-point tile accumulators, every tile owned by ONE workgroup (no row atomics on split levels)
   Options() {                                               // the environment is read ONCE, at first use
     if (const char *e = std::getenv("MSDA_GATHER")) gather = std::atoi(e);
     if (const char *e = std::getenv("MSDA_SCATTER_FIXED")) scatter_fixed = std::atoi(e) != 0;
@@ -347,7 +351,8 @@ inline TiledWorkspace tiled_workspace(int B, int M, int L, int Lq, int P) {
 inline size_t tiled_workspace_bytes(int B, int M, int L, int Lq, int P) { return tiled_workspace(B, M, L, Lq, P).bytes; }
 
 // Tiling of every level for the tile-owner scatter (msda_backward_tiled.hip, K2).
-msda::BwdPlan make_plan(const int64_t *shapes_host, const int64_t *lsi_host, int L, int Lq, int P) {
+// single_owner: every tile is scanned by one workgroup (n_chunks = 1) -- its write-back is plain stores, with no row atomics
+msda::BwdPlan make_plan(const int64_t *shapes_host, const int64_t *lsi_host, int L, int Lq, int P, bool single_owner = false) {
   msda::BwdPlan plan{};
   plan.n_levels = L;
   const long long n_pts = (long long)Lq * P;
@@ -370,7 +375,7 @@ msda::BwdPlan make_plan(const int64_t *shapes_host, const int64_t *lsi_host, int
     }
     const long long tiles = (long long)plan.n_ty[l] * plan.n_tx[l];
     const long long per_tile = (n_pts + tiles - 1) / tiles;
-    plan.n_chunks[l] = (int)std::max(1LL, std::min(8LL, (per_tile + target / 2) / target));
+    plan.n_chunks[l] = single_owner ? 1 : (int)std::max(1LL, std::min(8LL, (per_tile + target / 2) / target));
     work[l] = (double)per_tile / plan.n_chunks[l];
     plan.order[l] = l;
   }
@@ -402,6 +407,9 @@ int backward_impl(const T *value, const int64_t *shapes, const int64_t *lsi, con
   if (int e = check_dims(B, S, M, D, L, Lq, P)) return e;
   hipStream_t stream = (hipStream_t)stream_;
   const long long n_pairs = (long long)B * Lq * M;
+  // deterministic mode: the only f32 grad_value scatter whose additions run in a fixed order is the record-list scatter with
+  // integer (fixed-point) tile sums and single-owner tiles; the gather kernels write each gradient once (no far-point atomics)
+  const bool det = options().deterministic != 0;
   if ((vv.token_stride || vv.mask) && !(sizeof(T) == 4 && fused_ref && tiled_backward_applies(4, D, L, P) && M * L * 8 <= 1024))
     return MSDA_E_UNSUPPORTED;          // strided / masked value: fused d32 path only
 
@@ -422,7 +430,7 @@ int backward_impl(const T *value, const int64_t *shapes, const int64_t *lsi, con
       if (int e = check_host_geometry(shapes_host, lsi_host, L, S)) return e;
       // self-attention shape: row-tile scatter + window gather (no transposed lists, no LDS atomics per channel)
       const long long widest = std::max<long long>(std::max(loc_rs, aw_rs), std::max(M * 32, vv.token_stride));
-      if (options().scatter_rows && window_applies(true, shapes_host, lsi_host, Lq, S, widest) && (!fused_ref || fused_ref_dim == 2)) {
+      if (options().scatter_rows && !det && window_applies(true, shapes_host, lsi_host, Lq, S, widest) && (!fused_ref || fused_ref_dim == 2)) {
         msda::RowPlan rp;
         // ---- saved backward: exact scan lists (msda_bin.hip) -- one streaming pass over the saved locations bins every (query,
         // level) unit into the tiles its points fall into; the cell scatter scans exactly those, whatever the offsets look like
@@ -556,7 +564,7 @@ int backward_impl(const T *value, const int64_t *shapes, const int64_t *lsi, con
         }
       }
       if (saved || plan_mode) return MSDA_E_UNSUPPORTED;          // msda_fused_save_supported() said otherwise
-      const msda::BwdPlan plan = make_plan(shapes_host, lsi_host, L, Lq, P);
+      const msda::BwdPlan plan = make_plan(shapes_host, lsi_host, L, Lq, P, det);
       if ((long long)Lq * P >= (1LL << (62 - msda::kFixBits))) return MSDA_E_SHAPE;   // fixed-point headroom
       const TiledWorkspace ws = tiled_workspace(B, M, L, Lq, P);
       char *wsp = reinterpret_cast<char *>(workspace);
@@ -574,7 +582,7 @@ int backward_impl(const T *value, const int64_t *shapes, const int64_t *lsi, con
       // short record lists (the decoder's cross-attention): the row-band scatter (msda_backward_bands.hip) -- every level written
       // with plain stores, f32 sums in registers: no fixed-point bounds, no zero fill
       msda::BandPlan bp;
-      const bool bands = options().scatter_bands && options().scatter_sorted != 2 && L == 4 && P == 4 &&
+      const bool bands = !det && options().scatter_bands && options().scatter_sorted != 2 && L == 4 && P == 4 &&
                          msda::make_band_plan(shapes_host, lsi_host, Lq, bp);
       if (!bands) msda::bwd_bounds_kernel<<<B * M, 256, 0, stream>>>(boxes, bounds, (int)(L * ws.n_chunks_per_list));
       // levels shared by several workgroups are accumulated with atomics: zero exactly those rows
@@ -591,10 +599,10 @@ int backward_impl(const T *value, const int64_t *shapes, const int64_t *lsi, con
       } else
       // measured (B = 16, KITTI pyramid): sorted 0.90 ms vs 1.04 ms at Lq = 10200; 0.259 vs 0.245 at Lq = 550; 0.137 vs
       // 0.091 at Lq = 50 -- the batches' barriers only pay off on long record lists
-      if (options().scatter_sorted == 1 ? Lq * P >= 8192 : options().scatter_sorted == 2)
+      if (!det && (options().scatter_sorted == 1 ? Lq * P >= 8192 : options().scatter_sorted == 2))
         msda::bwd_scatter_sorted_kernel<<<8 * plan.n_items * bm_groups, msda::kSortThreads, 0, stream>>>(
             rec_hw, rec_aw, boxes, grad_out, grad_value, plan, B, S, M, Lq, P, (int)ws.n_chunks_per_list, vv.mask);
-      else if (scatter_fixed_point())
+      else if (det || scatter_fixed_point())
         msda::bwd_scatter_kernel<true><<<8 * plan.n_items * bm_groups, msda::kScatterThreads, 0, stream>>>(
             rec_hw, rec_aw, boxes, bounds, grad_out, grad_value, plan, B, S, M, Lq, P, (int)ws.n_chunks_per_list, vv.mask);
       else
@@ -645,6 +653,7 @@ int msda_set_option(const char *name, int value) {
   if (n == "plan_reach" && value >= 1 && value <= 16) { options().plan_reach = value; return 0; }
   if (n == "plan_fused" && (value == 0 || value == 1)) { options().plan_fused = value; return 0; }
   if (n == "scatter_lists_cap" && value >= 0) { options().scatter_lists_cap = value; return 0; }
+  if (n == "deterministic" && (value == 0 || value == 1)) { options().deterministic = value; return 0; }
   return MSDA_E_UNSUPPORTED;
 }
 
@@ -652,7 +661,7 @@ int msda_options_stamp(void) {
   // everything a plan made by msda_saved_plan_f32 depends on besides the call's own arguments
   const Options &o = options();
   unsigned h = 2166136261u;
-  for (int v : {o.directional, o.scatter_lists, o.scatter_rows, o.scatter_reach, o.plan_reach, o.plan_fused, o.window, o.window_halo, o.gather}) {
+  for (int v : {o.directional, o.scatter_lists, o.scatter_rows, o.scatter_reach, o.plan_reach, o.plan_fused, o.window, o.window_halo, o.gather, o.deterministic}) {
     h ^= (unsigned)v + 0x9E3779B9u;
     h *= 16777619u;
   }
@@ -882,7 +891,8 @@ int msda_fused_save_supported_view(int S, int M, int D, int L, int Lq, int P, in
   msda::RowPlan rp;
   // the widest row stride the view entry points will address a plane with (their 32-bit lane offsets: window_fits())
   const long long widest = std::max<long long>(std::max(offsets_row_stride, logits_row_stride), std::max(M * 32, value_token_stride));
-  return options().scatter_rows && window_applies(true, shapes_host, level_start_host, Lq, S, widest) &&
+  // (deterministic mode: the saved locations are laid out for the row-tile scatter, which that mode does not run)
+  return options().scatter_rows && !options().deterministic && window_applies(true, shapes_host, level_start_host, Lq, S, widest) &&
          window_applies(false, shapes_host, level_start_host, Lq, S, widest) &&
          msda::make_row_plan(shapes_host, level_start_host, options().scatter_reach, rp) ? 1 : 0;
 }

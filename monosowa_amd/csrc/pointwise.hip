@@ -597,7 +597,16 @@ inline int grid_for_vec(long long n_vec) {
 
 }  // namespace mono
 
+// Deterministic mode (mono_set_deterministic): process-wide, read at launch time by the GroupNorm and head-tail entry points.
+static int g_deterministic = 0;
+
 extern "C" {
+
+int mono_set_deterministic(int on) {
+  const int prev = g_deterministic;
+  g_deterministic = on != 0;
+  return prev;
+}
 
 int mono_reduce_blocks(long long rows);
 
@@ -989,7 +998,12 @@ int mono_groupnorm_nhwc_fwd_f32(const float *x, const float *pre_bias, const flo
   if (B <= 0 || HW <= 0 || C != mono::kGnC || G != mono::kGnG || B > 65535) return -2;
   hipStream_t st = (hipStream_t)stream_;
   const dim3 grid((HW + mono::kGnPix - 1) / mono::kGnPix, B);
-  mono::gn_stats_kernel<<<grid, 256, 0, st>>>(x, pre_bias, stats, HW);
+  if (g_deterministic) {
+    mono::gn_stats_kernel<true><<<grid, 256, 0, st>>>(x, pre_bias, stats, HW);
+    mono::gn_fold_kernel<<<B, 512, 0, st>>>(stats, (int)grid.x, mono::kGnG * 2);
+  } else {
+    mono::gn_stats_kernel<<<grid, 256, 0, st>>>(x, pre_bias, stats, HW);
+  }
   if (relu) mono::gn_apply_kernel<true><<<grid, 256, 0, st>>>(x, pre_bias, stats, gamma, beta, y, mean_rstd, HW, eps);
   else mono::gn_apply_kernel<false><<<grid, 256, 0, st>>>(x, pre_bias, stats, gamma, beta, y, mean_rstd, HW, eps);
   return (int)hipGetLastError();
@@ -997,6 +1011,17 @@ int mono_groupnorm_nhwc_fwd_f32(const float *x, const float *pre_bias, const flo
 
 // Rows of gbias scratch the backward needs: one per workgroup.
 int mono_groupnorm_blocks(int B, int HW) { return B * ((HW + mono::kGnPix - 1) / mono::kGnPix); }
+
+// Doubles of `stats` (forward) / `part` (backward): B * 64 / B * 512, plus, in deterministic mode, one row of partial sums per
+// workgroup behind them.  0 for invalid sizes.
+long long mono_groupnorm_stats_doubles(int B, int HW) {
+  if (B <= 0 || HW <= 0) return 0;
+  return (long long)mono::kGnG * 2 * (B + (g_deterministic ? mono_groupnorm_blocks(B, HW) : 0));
+}
+long long mono_groupnorm_part_doubles(int B, int HW) {
+  if (B <= 0 || HW <= 0) return 0;
+  return (long long)mono::kGnC * 2 * (B + (g_deterministic ? mono_groupnorm_blocks(B, HW) : 0));
+}
 
 // part [B, 256, 2] f64 must be zero on entry; on return part[b][c] = {sum gy' xhat, sum gy'} (ggamma / gbeta are its
 // sums over b).  y (the forward output) is read only when relu != 0.  With pre_bias: gbias [256] receives the bias
@@ -1009,7 +1034,13 @@ int mono_groupnorm_nhwc_bwd_f32(const float *gy, const float *x, const float *pr
   hipStream_t st = (hipStream_t)stream_;
   const dim3 grid((HW + mono::kGnPix - 1) / mono::kGnPix, B);
   float *gp = pre_bias ? gbias_partials : nullptr;
-  if (relu) {
+  if (g_deterministic) {
+    if (relu) mono::gn_bwd_stats_kernel<true, true><<<grid, 256, 0, st>>>(gy, x, pre_bias, y, mean_rstd, part, HW);
+    else mono::gn_bwd_stats_kernel<false, true><<<grid, 256, 0, st>>>(gy, x, pre_bias, y, mean_rstd, part, HW);
+    mono::gn_fold_kernel<<<B, 512, 0, st>>>(part, (int)grid.x, mono::kGnC * 2);
+    if (relu) mono::gn_bwd_apply_kernel<true><<<grid, 256, 0, st>>>(gy, x, pre_bias, y, mean_rstd, gamma, part, gx, gp, HW, ggamma_gbeta);
+    else mono::gn_bwd_apply_kernel<false><<<grid, 256, 0, st>>>(gy, x, pre_bias, y, mean_rstd, gamma, part, gx, gp, HW, ggamma_gbeta);
+  } else if (relu) {
     mono::gn_bwd_stats_kernel<true><<<grid, 256, 0, st>>>(gy, x, pre_bias, y, mean_rstd, part, HW);
     mono::gn_bwd_apply_kernel<true><<<grid, 256, 0, st>>>(gy, x, pre_bias, y, mean_rstd, gamma, part, gx, gp, HW, ggamma_gbeta);
   } else {
@@ -1130,6 +1161,13 @@ int mono_head_tail_bwd_f32(const float *tmp, const float *size3d, const float *d
   if (!tmp || !size3d || !depth_reg || !wdepth || !fu || !img_h || !g_tmp || !g_size3d || !g_depth_reg || !g_wdepth) return -1;
   if (B <= 0 || Q <= 0 || H <= 0 || W <= 0 || (ref && (ref_dim < 1 || ref_dim > 6))) return -2;
   const mono::HeadTailArgs a{tmp, size3d, depth_reg, wdepth, fu, img_h, B, Q, H, W, ref, ref_dim};
+  if (g_deterministic) {
+    if ((long long)H * W > mono::kHeadMapCap) return -3;
+    mono::head_tail_bwd_kernel<true><<<(B * Q + 255) / 256, 256, 0, (hipStream_t)stream>>>(a, g_coords, g_depth_ave, g_tmp, g_size3d,
+                                                                                         g_depth_reg, g_wdepth);
+    mono::head_tail_wdepth_kernel<<<B, 256, 0, (hipStream_t)stream>>>(a, g_depth_ave, g_wdepth);
+    return (int)hipGetLastError();
+  }
   mono::head_tail_bwd_kernel<<<(B * Q + 255) / 256, 256, 0, (hipStream_t)stream>>>(a, g_coords, g_depth_ave, g_tmp, g_size3d,
                                                                                    g_depth_reg, g_wdepth);
   return (int)hipGetLastError();

@@ -8,10 +8,11 @@ import os
 
 import torch
 
-from ._lib import on_device, raw_stream
+from ._lib import on_device, raw_stream, DeterministicSwitch
 
 _PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmonosowa_gemm.so")
-SYMBOLS = ("mono_gemm_nt_epilogue_f32", "mono_gemm_tn_bgrad_f32", "mono_gemm_nn_f32", "mono_gemm_set_autotune", "mono_gemm_cache_size")
+SYMBOLS = ("mono_gemm_nt_epilogue_f32", "mono_gemm_tn_bgrad_f32", "mono_gemm_nn_f32", "mono_gemm_set_autotune", "mono_gemm_cache_size",
+           "mono_gemm_set_deterministic")
 _lib = None
 
 
@@ -31,11 +32,17 @@ def load():
         lib.mono_gemm_set_autotune.restype = I
         lib.mono_gemm_set_autotune.argtypes = [I]
         lib.mono_gemm_cache_size.restype = I
+        lib.mono_gemm_set_deterministic.restype = I
+        lib.mono_gemm_set_deterministic.argtypes = [I]
         n = os.environ.get("MONOSOWA_GEMM_AUTOTUNE")              # candidates timed per problem key (default 32; 1: the library's first choice)
         if n is not None:
             lib.mono_gemm_set_autotune(int(n))
         _lib = lib
     return _lib
+
+
+# torch.use_deterministic_algorithms -> mono_gemm_set_deterministic (kernel selection without timing, cache keyed by the mode)
+DETERMINISTIC = DeterministicSwitch(lambda on: load().mono_gemm_set_deterministic(on))
 
 
 def _ok(t):
@@ -57,6 +64,7 @@ def gemm_nt(a, w, scale=None, bias=None, residual=None, relu=False, out=None):
     assert w.shape[1] == K and supported(a, w, residual)
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    DETERMINISTIC.sync()
     with on_device(a.device):
         code = load().mono_gemm_nt_epilogue_f32(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), _ptr(residual),
                                                 residual.stride(0) if residual is not None else N, out.data_ptr(), out.stride(0), M, N, K,
@@ -73,6 +81,7 @@ def gemm_tn_bgrad(gy, x, with_bias=True):
     assert x.shape[0] == M and supported(gy, x)
     gw = torch.empty((N, K), dtype=torch.float32, device=gy.device)
     gb = torch.empty((N,), dtype=torch.float32, device=gy.device) if with_bias else None
+    DETERMINISTIC.sync()
     with on_device(gy.device):
         code = load().mono_gemm_tn_bgrad_f32(gy.data_ptr(), gy.stride(0), x.data_ptr(), x.stride(0), gw.data_ptr(), K, _ptr(gb), M, N, K,
                                              raw_stream())
@@ -87,6 +96,7 @@ def gemm_nn(gy, w, out=None):
     K = w.shape[1]
     assert w.shape[0] == N and supported(gy, w)
     gx = torch.empty((M, K), dtype=torch.float32, device=gy.device) if out is None else out
+    DETERMINISTIC.sync()
     with on_device(gy.device):
         code = load().mono_gemm_nn_f32(gy.data_ptr(), gy.stride(0), w.data_ptr(), w.stride(0), gx.data_ptr(), gx.stride(0), M, N, K, raw_stream())
     if code:

@@ -16,6 +16,31 @@ from ..pointwise import conv_channel_bias, conv_group_norm, depth_expectation, d
 from ..token_linear import token_linear
 
 
+_LINEAR_WEIGHTS = {}
+
+
+def _linear_weights(n_in, n_out, device):
+    """[n_out, n_in] weights of F.interpolate(mode="linear", align_corners=False) along one axis: the interpolation of the
+    identity, so the coefficients are PyTorch's own."""
+    key = (n_in, n_out, device)
+    w = _LINEAR_WEIGHTS.get(key)
+    if w is None:
+        eye = torch.eye(n_in, device=device)[None]                                   # [1, n_in (channels), n_in]
+        w = _LINEAR_WEIGHTS[key] = F.interpolate(eye, size=n_out, mode="linear").squeeze(0).t().contiguous()
+    return w
+
+
+def upsample_bilinear(x, size):
+    """``F.interpolate(x, size, mode="bilinear")``.  Under torch.use_deterministic_algorithms, when a gradient is needed, as
+    two matrix products with the separable weights instead: ATen's bilinear upsample backward adds with atomics and refuses
+    to run in that mode, a product's backward is two more products (fixed order)."""
+    if not (torch.are_deterministic_algorithms_enabled() and torch.is_grad_enabled() and x.requires_grad):
+        return F.interpolate(x, size=size, mode="bilinear")
+    ah = _linear_weights(x.shape[-2], int(size[0]), x.device)
+    aw = _linear_weights(x.shape[-1], int(size[1]), x.device)
+    return torch.matmul(torch.matmul(ah, x), aw.t()).contiguous(memory_format=torch.channels_last)
+
+
 class DepthEncoderLayer(nn.Module):
     """Post-norm transformer encoder layer: q = k = src + pos, v = src (transformer.py:57-65)."""
 
@@ -91,7 +116,7 @@ class DepthPredictor(nn.Module):
         assert len(feature) == 4
         # Conv2d + GroupNorm(32, d) (+ ReLU) blocks: the norms run through the channels-last HIP kernels
         src_16 = conv_group_norm(feature[1], self.proj[0], self.proj[1])
-        src_32 = conv_group_norm(F.interpolate(feature[2], size=src_16.shape[-2:], mode="bilinear"), self.upsample[0], self.upsample[1])
+        src_32 = conv_group_norm(upsample_bilinear(feature[2], src_16.shape[-2:]), self.upsample[0], self.upsample[1])
         src_8 = conv_group_norm(feature[0], self.downsample[0], self.downsample[1])
         src = (src_8 + src_16 + src_32) / 3
         src = conv_group_norm(src, self.depth_head[0], self.depth_head[1], relu=True)

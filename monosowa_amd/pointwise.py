@@ -7,14 +7,15 @@ import numpy as np
 import torch
 
 from . import flops
-from ._lib import raw_stream, on_device
+from ._lib import raw_stream, on_device, DeterministicSwitch
 
 _PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmonosowa_pointwise.so")
 SYMBOLS = ("mono_bias_act_f32", "mono_bias_relu_maxpool_nhwc_f32", "mono_conv1x1_tail_f32", "mono_conv1x1_tail_ds_f32", "mono_conv1x1_head_f32", "mono_relu_grad_f32", "mono_relu_grad2_f32", "mono_relu_grad3_f32", "mono_bias_relu_mask_f32", "mono_relu_grad_mask_f32", "mono_affine_relu_mask_f32", "mono_affine_relu_grad_f32", "mono_dropout_add_layernorm_fwd_f32",
            "mono_dropout_add_layernorm_bwd_f32", "mono_groupnorm_nhwc_fwd_f32", "mono_groupnorm_nhwc_bwd_f32", "mono_groupnorm_blocks", "mono_colsum_f32", "mono_colsum_strided_f32", "mono_reduce_blocks", "mono_adamw_step_f32", "mono_relu_dropout_fwd_f32",
            "mono_relu_dropout_bwd_f32", "mono_matched_losses_fwd_f32", "mono_matched_losses_bwd_f32", "mono_ddn_loss_blocks",
            "mono_ddn_loss_fwd_f32", "mono_ddn_loss_bwd_f32", "mono_depth_expect_fwd_f32", "mono_depth_expect_bwd_f32", "mono_focal_fwd_f32", "mono_focal_bwd_f32", "mono_head_tail_fwd_f32", "mono_head_tail_bwd_f32", "mono_match_cost_f32", "mono_refine_reference_f32", "mono_relu_dropout_bwd_colsum_f32", "mono_sum_slices_f32", "mono_colsum_any_blocks", "mono_colsum_any_f32", "mono_relu_grad_mask3_f32", "mono_lsap_match_flat_f32",
-           "mono_linear_wgrad_workspace", "mono_linear_wgrad_f32", "mono_colsum_levels_blocks", "mono_colsum_levels_f32", "mono_relu_grad_scale_f32")
+           "mono_linear_wgrad_workspace", "mono_linear_wgrad_f32", "mono_colsum_levels_blocks", "mono_colsum_levels_f32", "mono_relu_grad_scale_f32",
+           "mono_set_deterministic", "mono_groupnorm_stats_doubles", "mono_groupnorm_part_doubles")
 _lib = None
 
 
@@ -65,6 +66,12 @@ def load():
         lib.mono_groupnorm_nhwc_bwd_f32.argtypes = [P] * 11 + [I, I, I, I, I, P]
         lib.mono_groupnorm_blocks.restype = I
         lib.mono_groupnorm_blocks.argtypes = [I, I]
+        lib.mono_groupnorm_stats_doubles.restype = LL
+        lib.mono_groupnorm_stats_doubles.argtypes = [I, I]
+        lib.mono_groupnorm_part_doubles.restype = LL
+        lib.mono_groupnorm_part_doubles.argtypes = [I, I]
+        lib.mono_set_deterministic.restype = I
+        lib.mono_set_deterministic.argtypes = [I]
         lib.mono_relu_dropout_fwd_f32.restype = I
         lib.mono_relu_dropout_fwd_f32.argtypes = [P, P, LL, F, U, P]
         lib.mono_colsum_any_blocks.restype = I
@@ -511,12 +518,19 @@ def zeros_f64(n, device):
     return out
 
 
+# torch.use_deterministic_algorithms -> mono_set_deterministic (GroupNorm statistics and the head tail's depth-map gradient)
+DETERMINISTIC = DeterministicSwitch(lambda on: load().mono_set_deterministic(on))
+
+
 class _GroupNormNHWC(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, pre_bias, weight, bias, eps, relu):
         B, C, H, W = x.shape
         y = torch.empty_like(x)                                       # keeps the channels_last strides
-        stats = zeros_f64(B * 32 * 2, x.device)
+        if DETERMINISTIC.sync():                                      # partial-sum slab behind the statistics, every element stored
+            stats = torch.empty(load().mono_groupnorm_stats_doubles(B, H * W), dtype=torch.float64, device=x.device)
+        else:
+            stats = zeros_f64(B * 32 * 2, x.device)
         mean_rstd = torch.empty(B, 32, 2, dtype=torch.float32, device=x.device)
         with on_device(x.device):
             code = load().mono_groupnorm_nhwc_fwd_f32(x.data_ptr(), pre_bias.data_ptr() if pre_bias is not None else None,
@@ -535,7 +549,10 @@ class _GroupNormNHWC(torch.autograd.Function):
         B, C, H, W = x.shape
         gy = gy.contiguous(memory_format=torch.channels_last)
         gx = torch.empty_like(x)
-        part = zeros_f64(B * C * 2, x.device)
+        if DETERMINISTIC.sync():
+            part = torch.empty(load().mono_groupnorm_part_doubles(B, H * W), dtype=torch.float64, device=x.device)
+        else:
+            part = zeros_f64(B * C * 2, x.device)
         gwb = torch.empty(2, C, dtype=torch.float32, device=x.device)
         lib = load()
         gbias = partials = None
@@ -1138,7 +1155,7 @@ class _HeadTail(torch.autograd.Function):
         B, Q, _ = tmp.shape
         H, W = wdepth.shape[-2:]
         g_tmp, g_size, g_dreg = torch.empty_like(tmp), torch.empty_like(size3d), torch.empty_like(depth_reg)
-        g_wd = torch.zeros_like(wdepth)
+        g_wd = torch.empty_like(wdepth) if DETERMINISTIC.sync() else torch.zeros_like(wdepth)     # (that mode stores the whole map)
         gc = g_coords.contiguous() if g_coords is not None else None
         gd = g_dave.contiguous() if g_dave is not None else None
         rp, rd = (ref.data_ptr(), ref.shape[-1]) if ref is not None else (None, 0)
@@ -1155,7 +1172,11 @@ class _HeadTail(torch.autograd.Function):
 def head_tail_supported(tmp, size3d, depth_reg, wdepth, fu, img_h):
     f = torch.float32
     return tmp.is_cuda and all(t.dtype == f for t in (tmp, size3d, depth_reg, wdepth, fu, img_h)) and tmp.shape[-1] == 6 \
-        and size3d.shape[-1] == 3 and depth_reg.shape[-1] == 2 and wdepth.dim() == 3 and not fu.requires_grad and not img_h.requires_grad
+        and size3d.shape[-1] == 3 and depth_reg.shape[-1] == 2 and wdepth.dim() == 3 and not fu.requires_grad and not img_h.requires_grad \
+        and not (torch.are_deterministic_algorithms_enabled() and wdepth.shape[-2] * wdepth.shape[-1] > HEAD_MAP_CAP)
+
+
+HEAD_MAP_CAP = 12288      # deterministic mode: the largest depth map head_tail_wdepth_kernel holds in LDS (head_tail.hip kHeadMapCap)
 
 
 def head_tail(tmp, size3d, depth_reg, wdepth, fu, img_h, ref=None):

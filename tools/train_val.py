@@ -31,7 +31,7 @@ from monosowa_amd.helpers.save_helper import load_checkpoint              # noqa
 from monosowa_amd.helpers.scheduler_helper import build_lr_scheduler      # noqa: E402
 from monosowa_amd.helpers.tester_helper import Tester                     # noqa: E402
 from monosowa_amd.helpers.trainer_helper import Trainer                   # noqa: E402
-from monosowa_amd.helpers.utils_helper import create_logger, set_random_seed   # noqa: E402
+from monosowa_amd.helpers.utils_helper import create_logger, set_deterministic, set_random_seed   # noqa: E402
 
 
 def main():
@@ -43,6 +43,7 @@ def main():
     assert os.path.exists(args.config)
     cfg = yaml.load(open(args.config, "r"), Loader=yaml.Loader)
     set_random_seed(cfg.get("random_seed", 444))
+    set_deterministic(cfg.get("trainer"))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
