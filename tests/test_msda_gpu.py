@@ -1487,14 +1487,26 @@ def test_level_embed_gradient_from_the_encoder_blocks():
     """The whole transformer (train mode, dropout 0 so both paths see the same arithmetic) with the level_embed gradient
     produced inside the encoder blocks from per-level column sums, against the path where pos carries the gradient:
     level_embed.grad, the feature gradients and a few parameter gradients."""
+    _level_embed_gradient_paths(0.0)
+
+
+def test_level_embed_gradient_from_the_encoder_blocks_with_dropout():
+    """The same with dropout 0.1 (attention dropout off): both paths draw their dropout seeds in the same order on the same
+    layouts, so with the seed counters reset before each they apply identical masks."""
+    drawn = _level_embed_gradient_paths(0.1)
+    assert drawn[0] == drawn[1] >= 3 * 3 + 3 * 5, drawn          # LayerNorm and ReLU-dropout masks of every layer
+
+
+def _level_embed_gradient_paths(dropout):
     import yaml
+    from monosowa_amd import flash_attn, pointwise
     from monosowa_amd.monodetr import depthaware_transformer as T
     cfg = yaml.safe_load(open(os.path.join(os.path.dirname(os.path.dirname(__file__)), "configs", "monodetr.yaml")))["model"]
     torch.manual_seed(0)
-    tr = T.build_depthaware_transformer(dict(cfg, dropout=0.0)).cuda().train()
+    tr = T.build_depthaware_transformer(dict(cfg, dropout=dropout)).cuda().train()
     for m in tr.modules():
         if isinstance(m, (torch.nn.Dropout, torch.nn.MultiheadAttention)):
-            m.p = 0.0 if isinstance(m, torch.nn.Dropout) else None
+            m.p = dropout if isinstance(m, torch.nn.Dropout) else None
             if isinstance(m, torch.nn.MultiheadAttention):
                 m.dropout = 0.0
     tr.decoder.bbox_embed = torch.nn.ModuleList([T.MLP(256, 256, 6, 3) for _ in range(3)]).cuda()
@@ -1512,15 +1524,23 @@ def test_level_embed_gradient_from_the_encoder_blocks():
         T.LEVEL_EMBED_IN_BLOCK = flag
         for t in srcs + params:
             t.grad = None
+        torch.manual_seed(1)
+        pointwise._seed_counter[0] = flash_attn._seed_counter[0] = 0
         try:
             hs = tr(srcs, masks, pos, query, dpe, dpe, all_valid=True)[0]
         finally:
             T.LEVEL_EMBED_IN_BLOCK = True
         hs.square().mean().backward()
+        drawn.append(pointwise._seed_counter[0])
         return [hs.detach().clone()] + [t.grad.clone() for t in params + srcs]
-    a, b = run(True), run(False)
+    counters, drawn = (pointwise._seed_counter[0], flash_attn._seed_counter[0]), []
+    try:
+        a, b = run(True), run(False)
+    finally:
+        pointwise._seed_counter[0], flash_attn._seed_counter[0] = counters
     for x, y, n in zip(a, b, ["hs", "level_embed", "offsets.weight", "linear1.bias"] + ["src%d" % i for i in range(4)]):
         assert (x - y).abs().max() <= 1e-4 * max(y.abs().max().item(), 1e-6), n
+    return drawn
 
 
 def test_strided_fused_operator_reads_a_merged_projection_in_place():
