@@ -285,16 +285,11 @@ def test_fused_training_path_tracks_the_module_by_module_path(config):
     backbone_name, resolution, batch, mixed = _STEP_CONFIGS[config]
     import copy
     import yaml
-    from monosowa_amd import encoder_block, ms_deform_attn, pointwise
+    from fused_switches import fused_switches
     from monosowa_amd.helpers.model_helper import build_model, to_mi355x_layout
     from monosowa_amd.helpers.optimizer_helper import build_optimizer
-    from monosowa_amd.monodetr import backbone, criterion, depthaware_transformer, matcher, monodetr, position_encoding
+    from monosowa_amd.monodetr import criterion
     from monosowa_amd.synthetic import make_batch, prepare_targets
-    switches = [(criterion, "FUSED_MATCHED"), (depthaware_transformer, "ENCODER_BLOCKS"), (depthaware_transformer, "LEVEL_EMBED_IN_BLOCK"),
-                (depthaware_transformer, "MERGE_SA_PROJ"), (depthaware_transformer, "SELF_ATTN_HIP"), (monodetr, "MERGE_HEADS"),
-                (monodetr, "REUSE_BBOX_RAW"), (ms_deform_attn, "MERGED_PROJ"), (encoder_block, "MERGED_PROJ"),
-                (backbone, "AFFINE_IN_KERNEL"), (backbone, "CACHE_SCALE_SHIFT"), (pointwise, "USE_RELU_MASK"),
-                (matcher, "BLOCK_COST"), (position_encoding, "CACHE_ALL_VALID")]
     cfg = yaml.safe_load(open(os.path.join(os.path.dirname(os.path.dirname(__file__)), "configs", "monodetr.yaml")))
     mcfg = dict(cfg["model"], device="cuda", dropout=0.0, backbone=backbone_name, pretrained=False,
                 depth_map_size=(resolution[0] // 16, resolution[1] // 16))
@@ -312,10 +307,7 @@ def test_fused_training_path_tracks_the_module_by_module_path(config):
         assert len(set(calibs[:, 0, 0].tolist())) == 3 and len(set(info["canonical_scale"].tolist())) == 3
 
     def run(on):
-        saved = [(mod, name, getattr(mod, name)) for mod, name in switches]
-        for mod, name in switches:
-            setattr(mod, name, on)
-        try:
+        with fused_switches(on):                     # every listed switch; a renamed one fails instead of becoming a no-op
             model = to_mi355x_layout(copy.deepcopy(model0).cuda()).train()
             opt = build_optimizer(cfg["optimizer"], model)
             if not on:
@@ -332,9 +324,6 @@ def test_fused_training_path_tracks_the_module_by_module_path(config):
                      model.depthaware_transformer.encoder.layers[1].self_attn.sampling_offsets.weight.detach().clone(),
                      model.backbone[0].body.layer3[2].conv2.weight.detach().clone(), model.class_embed[0].weight.detach().clone()]
             return losses, probe
-        finally:
-            for mod, name, val in saved:
-                setattr(mod, name, val)
     l_on, w_on = run(True)
     l_off, w_off = run(False)
     for a, b in zip(l_on, l_off):
