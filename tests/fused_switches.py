@@ -49,6 +49,8 @@ SWITCHES = (
     ("monosowa_amd.monodetr.criterion", "FUSED_FOCAL", True, False),
     ("monosowa_amd.monodetr.criterion", "FUSED_MATCHED", True, False),
     ("monosowa_amd.monodetr.losses", "FUSED_DDN", True, False),
+    # detection extraction
+    ("monosowa_amd.helpers.decode_helper", "DEVICE_KERNEL", True, False),
 )
 
 

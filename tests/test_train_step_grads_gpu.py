@@ -16,12 +16,12 @@ The matching is discrete: F's [3, NL, K] indices are recorded and handed to P an
 import copy
 import os
 
-import numpy as np
 import pytest
 import torch
 import yaml
 
 from backbone_reference import _model, _reference
+from detector_reference import _Body, _FrozenMatcher, trained_like_msda
 from fused_switches import fused_switches
 
 pytestmark = pytest.mark.gpu
@@ -129,35 +129,6 @@ def test_backbone_and_input_projection_gradients_equal_float64(name, hw):
 
 
 # --------------------------------------------------------------------------------------------------------------- detector
-class _Body(torch.nn.Module):
-    """backbone body stand-in: the fixed C3 / C4 / C5 leaves (the Backbone wraps them as all-valid NestedTensors)"""
-    def __init__(self):
-        super().__init__()
-        self.feats = None
-
-    def forward(self, images):
-        return {str(i): f for i, f in enumerate(self.feats)}
-
-
-class _FrozenMatcher(torch.nn.Module):
-    """The first evaluation's assignment for every later one: ``match_layers_begin`` runs as usual, and
-    ``match_layers_end_flat`` returns the [3, NL, K] indices recorded from the first call (criterion.py forward_fast)."""
-    def __init__(self, inner):
-        super().__init__()
-        self.inner = inner
-        self.idx = None
-
-    def match_layers_begin(self, *args, **kwargs):
-        return self.inner.match_layers_begin(*args, **kwargs)
-
-    def match_layers_end_flat(self, handle):
-        got = self.inner.match_layers_end_flat(handle)
-        if self.idx is None:
-            self.idx = (got.cpu().numpy() if torch.is_tensor(got) else np.asarray(got)).copy()
-            return got
-        return self.idx.copy()
-
-
 LOSS_KEYS = [k + s for s in ("", "_0", "_1") for k in ("loss_ce", "loss_center", "loss_bbox", "loss_giou", "loss_depth", "loss_dim",
                                                        "loss_angle")] + ["loss_depth_map"]
 
@@ -198,16 +169,8 @@ def test_every_parameter_gradient_of_a_train_step_equals_float64(case):
             m.p = 0.0
         if isinstance(m, torch.nn.MultiheadAttention):
             m.dropout = 0.0
-    # sampling offsets away from the initial integer grid and attention logits away from uniform (a checkpoint's are): at the
-    # grid every sampling location sits on a pixel border, where d(location) jumps and f32 and f64 take different sides
-    from monosowa_amd.ms_deform_attn import MSDeformAttn
     gen = torch.Generator().manual_seed(23)
-    with torch.no_grad():
-        for m in model0.modules():
-            if isinstance(m, MSDeformAttn):
-                for lin, bias_scale in ((m.sampling_offsets, 0.5), (m.attention_weights, 0.3)):
-                    lin.weight.copy_(torch.randn(lin.weight.shape, generator=gen) * 0.02)
-                    lin.bias.add_((torch.rand(lin.bias.shape, generator=gen) - 0.5) * 2 * bias_scale)
+    trained_like_msda(model0, gen)
     model0.backbone[0].body = _Body()
     crit.matcher = _FrozenMatcher(crit.matcher)
     crit = crit.cuda().train()
