@@ -247,7 +247,8 @@ __global__ __launch_bounds__(kFocalThreads) void focal_fwd_kernel(const FocalArg
     float ce = 0.f;
     for (int b = 0; b < a.B; ++b) ce += fabsf((float)card[b] - a.sizes[b]);
     out[l * 3] = tot;
-    out[l * 3 + 1] = a.K > 0 ? 100.f - (float)correct * (100.f / (float)a.K) : 100.f;
+    // 100 * wrong / K, not 100 - 100 * correct / K: the subtraction cancels the leading digits of a small error
+    out[l * 3 + 1] = a.K > 0 ? 100.f * (float)(a.K - correct) / (float)a.K : 100.f;
     out[l * 3 + 2] = ce / (float)a.B;
   }
 }

@@ -372,10 +372,11 @@ class SetCriterion(nn.Module):
         per_layer["loss_ce"] = focal.mean(2).sum((1, 2)) / num_boxes * Q
         matched_logits = take(logits)
         if K:
-            correct = matched_logits.argmax(-1).eq(tgt_cls).float().sum(1) * (100.0 / K)
+            # 100 * wrong / K, not 100 - 100 * correct / K: the subtraction cancels the leading digits of a small error
+            wrong = K - matched_logits.argmax(-1).eq(tgt_cls).float().sum(1)
+            per_layer["class_error"] = wrong * 100.0 / K
         else:
-            correct = torch.zeros(NL, device=dev)
-        per_layer["class_error"] = 100 - correct
+            per_layer["class_error"] = torch.full((NL,), 100.0, device=dev)
         tgt_lengths = _dev(sizes, torch.float, dev)
         card_pred = (logits.argmax(-1) != C - 1).sum(2).float()
         per_layer["cardinality_error"] = (card_pred - tgt_lengths).abs().mean(1)
