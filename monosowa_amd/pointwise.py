@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import flops
-from ._lib import raw_stream, on_device, DeterministicSwitch
+from ._lib import raw_stream, on_device, DeterministicSwitch, alert_not_deterministic
 
 _PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmonosowa_pointwise.so")
 SYMBOLS = ("mono_bias_act_f32", "mono_bias_relu_maxpool_nhwc_f32", "mono_conv1x1_tail_f32", "mono_conv1x1_tail_ds_f32", "mono_conv1x1_head_f32", "mono_relu_grad_f32", "mono_relu_grad2_f32", "mono_relu_grad3_f32", "mono_bias_relu_mask_f32", "mono_relu_grad_mask_f32", "mono_affine_relu_mask_f32", "mono_affine_relu_grad_f32", "mono_dropout_add_layernorm_fwd_f32",
@@ -1155,7 +1155,14 @@ class _HeadTail(torch.autograd.Function):
         B, Q, _ = tmp.shape
         H, W = wdepth.shape[-2:]
         g_tmp, g_size, g_dreg = torch.empty_like(tmp), torch.empty_like(size3d), torch.empty_like(depth_reg)
-        g_wd = torch.empty_like(wdepth) if DETERMINISTIC.sync() else torch.zeros_like(wdepth)     # (that mode stores the whole map)
+        det = DETERMINISTIC.sync()
+        if det and H * W > HEAD_MAP_CAP:
+            # a direct caller above the cap (the model asks head_tail_supported first): only the atomic kernel covers such a map
+            alert_not_deterministic("head_tail", "the depth-map gradient of a map of more than %d cells is added with float "
+                                    "atomics" % HEAD_MAP_CAP)
+            DETERMINISTIC.force(False)                         # (warn_only: run it as it is)
+            det = False
+        g_wd = torch.empty_like(wdepth) if det else torch.zeros_like(wdepth)     # (that mode stores the whole map)
         gc = g_coords.contiguous() if g_coords is not None else None
         gd = g_dave.contiguous() if g_dave is not None else None
         rp, rd = (ref.data_ptr(), ref.shape[-1]) if ref is not None else (None, 0)

@@ -134,3 +134,38 @@ def test_trainer_deterministic_key_reaches_torch(torch_flag, monkeypatch):
     assert os.environ["CUBLAS_WORKSPACE_CONFIG"] == ":4096:8"
     with open(os.path.join(ROOT, "tools", "train_val.py")) as f:
         assert 'set_deterministic(cfg.get("trainer"))' in f.read()
+
+
+# 4 x the plain float32 F.interpolate's own error against float64 on the CPU over exactly these sizes (forward 9.4e-7, gradient
+# 8.9e-7, worst at (5, 17) -> (9, 33)), rounded up; the matrix-product form measured 9.5e-7 / 9.1e-7
+BOUND_UPSAMPLE = 4e-6
+UPSAMPLE_SIZES = [((6, 20), (12, 40)), ((5, 17), (9, 33)), ((3, 9), (5, 17)), ((12, 40), (24, 80)), ((12, 44), (24, 88)),
+                  ((1, 1), (2, 3)), ((7, 9), (7, 9))]
+
+
+@pytest.mark.parametrize("src,dst", UPSAMPLE_SIZES)
+def test_upsample_bilinear_as_matrix_products_equals_float64_interpolate(torch_flag, src, dst):
+    """depth_predictor.upsample_bilinear under the flag with a gradient wanted (two matrix products with the separable weights):
+    forward and input gradient against F.interpolate(mode="bilinear") in float64; the output is channels-last."""
+    import torch.nn.functional as F
+    from monosowa_amd.monodetr.depth_predictor import upsample_bilinear
+    torch.manual_seed(src[0] * 100 + dst[1])
+    x = torch.randn(2, 256, *src)
+    gy = torch.randn(2, 256, *dst)
+    xr = x.double().requires_grad_(True)
+    ref = F.interpolate(xr, size=dst, mode="bilinear")
+    g_ref, = torch.autograd.grad(ref, xr, gy.double())
+    torch.use_deterministic_algorithms(True)
+    xd = x.clone().requires_grad_(True)
+    y = upsample_bilinear(xd, dst)
+    assert y.shape == ref.shape and y.is_contiguous(memory_format=torch.channels_last)
+    assert y.grad_fn is not None and "Upsample" not in type(y.grad_fn).__name__          # the matrix-product form did run
+    g, = torch.autograd.grad(y, xd, gy)
+    for name, got, want in (("forward", y, ref), ("grad_input", g, g_ref)):
+        err = ((got.double() - want).abs().max() / want.abs().max().clamp_min(1e-30)).item()
+        print("upsample_bilinear %s -> %s %s: e_D = %.2e" % (src, dst, name, err))
+        assert err <= BOUND_UPSAMPLE, (name, err)
+    # without a gradient wanted, or with the flag off, the function is F.interpolate itself
+    assert torch.equal(upsample_bilinear(x, dst), F.interpolate(x, size=dst, mode="bilinear"))
+    torch.use_deterministic_algorithms(False)
+    assert torch.equal(upsample_bilinear(xd, dst), F.interpolate(xd, size=dst, mode="bilinear"))

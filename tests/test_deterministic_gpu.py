@@ -1,6 +1,7 @@
 """Deterministic mode (torch.use_deterministic_algorithms) on the GPU: the native backward kernels give bitwise-identical
-gradients run after run -- also with another kernel running beside them -- and still meet the f64-oracle tolerances that
-tests/test_msda_gpu.py applies to the default kernels; a path without a deterministic variant refuses to run."""
+gradients run after run -- also with another kernel running beside them; a path without a deterministic variant refuses to
+run.  That they still meet the f64-oracle tolerances that tests/test_msda_gpu.py applies to the default kernels is checked here on
+one sample per case only: tests/test_deterministic_parity_gpu.py holds that claim, for every kernel the mode selects."""
 import warnings
 
 import numpy as np

@@ -327,10 +327,35 @@ def _masks(draws, kinds):
     return [d.mask() for d in draws]
 
 
+@pytest.fixture
+def deterministic():
+    """torch's global flag on for the test, restored afterwards (warn_only included)."""
+    was, warn_only = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    torch.use_deterministic_algorithms(True)
+    yield
+    torch.use_deterministic_algorithms(was, warn_only=warn_only)
+
+
+def _ran_deterministic(value_like, shapes, lsi, Lq):
+    """dropout > 0 together with the recomputing MSDA backward is what a deterministic training run executes"""
+    from monosowa_amd import MultiScaleDeformableAttention as MSDA, _lib
+    assert _lib.MSDA_DETERMINISTIC.sync() is True and pointwise.DETERMINISTIC.sync() is True
+    assert not MSDA.fused_save_supported(value_like, shapes, lsi, Lq)
+
+
 def test_visual_encoder_layer_blocks_in_train_mode_match_pytorch_with_the_replayed_masks():
     """The encoder's two autograd nodes (encoder_block) with dropout p against F.linear / F.layer_norm and the product's
     MSDA operator, dropout as a multiplication by the probed masks (attention LN, FFN ReLU-dropout, FFN LN): output, d src,
     d pos and every parameter gradient -- the fused bias sums of output_proj, linear2 and linear1 included."""
+    _check_visual_encoder_layer_blocks(False)
+
+
+def test_visual_encoder_layer_blocks_in_train_mode_match_pytorch_under_the_deterministic_flag(deterministic):
+    """The same comparison, same bounds, under torch.use_deterministic_algorithms(True)."""
+    _check_visual_encoder_layer_blocks(True)
+
+
+def _check_visual_encoder_layer_blocks(det):
     from monosowa_amd.monodetr import depthaware_transformer as T
     torch.manual_seed(0)
     layer = T.VisualEncoderLayer(256, 256, 0.1, "relu", 4, 8, 4).cuda().train()
@@ -341,6 +366,8 @@ def test_visual_encoder_layer_blocks_in_train_mode_match_pytorch_with_the_replay
     ref = torch.rand(B, S, 4, 2, device="cuda")
     go = torch.randn(B, S, 256, device="cuda")
     names, params = zip(*layer.named_parameters())
+    if det:
+        _ran_deterministic(torch.empty(B, S, 8, 32, device="cuda"), shapes, lsi, S)
     with R.record() as draws:
         y = layer(src, pos, ref, shapes, lsi, None)
     assert "FFNBlock" in type(y.grad_fn).__name__
@@ -368,6 +395,15 @@ def test_visual_encoder_layer_blocks_in_train_mode_match_pytorch_with_the_replay
 def test_depth_aware_decoder_layer_in_train_mode_matches_pytorch_with_the_replayed_masks():
     """DepthAwareDecoderLayer (dropout 0.1, attention dropout off) at B = 16, 550 queries: its four fused LayerNorm dropouts and
     its ReLU-dropout against the same layer with F.layer_norm(x + z * mask) / relu(h) * mask in their place."""
+    _check_depth_aware_decoder_layer(False)
+
+
+def test_depth_aware_decoder_layer_in_train_mode_matches_pytorch_under_the_deterministic_flag(deterministic):
+    """The same comparison, same bounds, under torch.use_deterministic_algorithms(True)."""
+    _check_depth_aware_decoder_layer(True)
+
+
+def _check_depth_aware_decoder_layer(det):
     from monosowa_amd.monodetr import depthaware_transformer as T
     torch.manual_seed(1)
     layer = T.DepthAwareDecoderLayer(256, 256, 0.1, "relu", 4, 8, 4, group_num=11, group_size=50).cuda().train()
@@ -382,6 +418,8 @@ def test_depth_aware_decoder_layer_in_train_mode_matches_pytorch_with_the_replay
     go = torch.randn(B, Q, 256, device="cuda")
     names, params = zip(*[(n, p_) for n, p_ in layer.named_parameters()])
     leaves = (tgt, qpos, memory, dpe) + params
+    if det:
+        _ran_deterministic(torch.empty(B, S, 8, 32, device="cuda"), shapes, lsi, Q)
 
     def run():
         for t in leaves:

@@ -10,11 +10,16 @@ dropout 0) behind a backbone body that returns fixed C3 / C4 / C5 leaves, throug
 evaluated three times from identical weights, features and targets:
   F  float32, every switch at its shipped value (the product),
   P  float32, every switch of tests/fused_switches.py at its plain-PyTorch value,
-  R  float64, every switch plain (the f64 MSDA kernels are pinned to the C oracle by tests/test_msda_gpu.py).
-The matching is discrete: F's [3, NL, K] indices are recorded and handed to P and R.  F is compared with R per tensor by
-||g - g_ref|| / ||g_ref||; P must meet the same bound, so no bound is tighter than honest float32 arithmetic."""
+  R  float64, every switch plain (the f64 MSDA kernels are pinned to the C oracle by tests/test_msda_gpu.py),
+  D  F's switches under torch.use_deterministic_algorithms(True): the kernels a deterministic training run selects.
+The matching is discrete: F's [3, NL, K] indices are recorded and handed to P, R and D.  F and D are compared with R per tensor
+by ||g - g_ref|| / ||g_ref||; P must meet the same bound, so no bound is tighter than honest float32 arithmetic.  D is evaluated
+twice: every gradient has the same bits both times."""
+import collections
+import contextlib
 import copy
 import os
+import time
 
 import pytest
 import torch
@@ -23,21 +28,23 @@ import yaml
 from backbone_reference import _model, _reference
 from detector_reference import _Body, _FrozenMatcher, trained_like_msda
 from fused_switches import fused_switches
+from test_eval_forward_gpu import _patched
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # Per-tensor bounds on ||g - g_ref|| / ||g_ref||, one per group.  Measured on the MI355X (worst tensor of the group over
-# every case of this module): e_F = product vs float64, e_P = plain float32 vs float64.
+# every case of this module): e_F = product vs float64, e_P = plain float32 vs float64, e_D = product under the deterministic flag
+# vs float64 (D runs MIOpen under cudnn.deterministic, whose other convolution algorithms move the few pixel-border steps).
 # The float32 runs step across pixel borders that float64 does not (d(location) of MSDA jumps there) and through
-# convolution algorithms of the library; both show in e_P as much as in e_F.  Measured worst tensor, e_F / e_P:
-BOUND_BACKBONE = 1e-2      # 2.2e-3 / 2.7e-3 (ResNet-101 96 x 320, ResNet-50 136 x 520: the library's 3x3 convolutions)
-BOUND_INPUT_PROJ = 3e-3    # 7.0e-4 / 7.0e-4 (input_proj.2, 640 x 192)
-BOUND_ENCODER = 1.5e-2     # 4.2e-3 / 4.2e-3 (layer 0 sampling_offsets, 640 x 192; level_embed 2.1e-3 / 2.1e-3)
-BOUND_DECODER = 2.5e-2     # 8.5e-3 / 8.5e-3 (reference_points.bias, 640 x 192 at batch 13)
-BOUND_DEPTH = 2e-3         # 7.8e-4 / 7.8e-4 (downsample.0, 640 x 192 at batch 13)
-BOUND_HEADS = 6e-3         # 1.7e-3 / 1.1e-3 (dim_embed.0 / bbox_embed.2 first layers, 640 x 192)
-BOUND_LOSS = 2e-6          # 3.1e-7 / 3.5e-7: relative error of each differentiable loss term
+# convolution algorithms of the library; both show in e_P as much as in e_F.  Measured worst tensor, e_F / e_P; e_D behind it:
+BOUND_BACKBONE = 1e-2      # 2.2e-3 / 2.7e-3 (ResNet-101 96 x 320, ResNet-50 136 x 520: the library's 3x3 convolutions); e_D 1.9e-3
+BOUND_INPUT_PROJ = 3e-3    # 7.0e-4 / 7.0e-4 (input_proj.2, 640 x 192); e_D 3.3e-4 (feature C3, batch 13)
+BOUND_ENCODER = 1.5e-2     # 4.2e-3 / 4.2e-3 (layer 0 sampling_offsets, 640 x 192; level_embed 2.1e-3 / 2.1e-3); e_D 1.1e-3 (batch 13)
+BOUND_DECODER = 2.5e-2     # 8.5e-3 / 8.5e-3 (reference_points.bias, 640 x 192 at batch 13); e_D 8.5e-3 (the same tensor)
+BOUND_DEPTH = 2e-3         # 7.8e-4 / 7.8e-4 (downsample.0, 640 x 192 at batch 13); e_D 8.6e-5 (the same tensor)
+BOUND_HEADS = 6e-3         # 1.7e-3 / 1.1e-3 (dim_embed.0 / bbox_embed.2 first layers, 640 x 192); e_D 7.1e-4 (bbox_embed.1, batch 13)
+BOUND_LOSS = 2e-6          # 3.1e-7 / 3.5e-7: relative error of each differentiable loss term; e_D 3.1e-7
 
 
 def _rel_norm(g, ref):
@@ -57,6 +64,37 @@ def _node_names(roots):
         names.add(type(fn).__name__)
         stack.extend(nxt for nxt, _ in fn.next_functions)
     return names
+
+
+@contextlib.contextmanager
+def _mode(det):
+    """torch's deterministic flag (and MIOpen's switch, as a deterministic training run sets both) for one evaluation"""
+    was, warn_only = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    miopen = torch.backends.cudnn.deterministic
+    torch.use_deterministic_algorithms(det)
+    torch.backends.cudnn.deterministic = det or miopen
+    try:
+        yield
+    finally:
+        torch.use_deterministic_algorithms(was, warn_only=warn_only)
+        torch.backends.cudnn.deterministic = miopen
+
+
+@contextlib.contextmanager
+def _msda_backward_calls():
+    """counts the fused operator's two backward entry points: re-evaluated prologue / saved prologue"""
+    from monosowa_amd import MultiScaleDeformableAttention as MSDA
+    calls = collections.Counter()
+
+    def wrap(name):
+        fn = getattr(MSDA, name)
+
+        def spy(*args, **kwargs):
+            calls[name] += 1
+            return fn(*args, **kwargs)
+        return spy
+    with _patched([(MSDA, n, wrap(n)) for n in ("ms_deform_attn_fused_backward_merged", "ms_deform_attn_fused_backward_merged_saved")]):
+        yield calls
 
 
 def _report(title, errs):
@@ -90,10 +128,13 @@ def test_backbone_and_input_projection_gradients_equal_float64(name, hw):
     x = images.cuda().contiguous(memory_format=torch.channels_last)
     cot = None
 
-    def run(on):
+    def run(on, det=False):
         nonlocal cot
         model.zero_grad(set_to_none=True)
-        with fused_switches(on):
+        with fused_switches(on), _mode(det):
+            if det:
+                from monosowa_amd import gemm_lt, pointwise
+                assert pointwise.DETERMINISTIC.sync() is True and gemm_lt.DETERMINISTIC.sync() is True
             features, pos = model.backbone(x)
             srcs, _, _ = model.project_features(features, pos)
             nodes = _node_names(srcs)
@@ -104,6 +145,8 @@ def test_backbone_and_input_projection_gradients_equal_float64(name, hw):
 
     plain, plain_nodes = run(False)
     got, nodes = run(True)
+    # D: the pre-bias GroupNorm and the epilogue GEMMs under the flag, MIOpen under cudnn.deterministic (the two ResNet-50 cases)
+    got_d, nodes_d = run(True, det=True) if name == "resnet50" else (None, None)
 
     leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items() if _backbone_leaf(k)}
     _, want = _reference(dict(sd, **leaves), name, images.double())
@@ -126,6 +169,14 @@ def test_backbone_and_input_projection_gradients_equal_float64(name, hw):
     for fused in ("_AffineReluBackward", "_Conv1x1BnActBackward", "_GroupNormNHWCBackward"):
         assert fused in nodes, (fused, sorted(nodes))
     assert "_BiasActForkBackward" in plain_nodes and "_Conv1x1BnActBackward" not in plain_nodes, sorted(plain_nodes)
+    if got_d is not None:
+        assert {n for n, g in got_d.items() if g is not None} == set(leaves)
+        assert {"_AffineReluBackward", "_Conv1x1BnActBackward", "_GroupNormNHWCBackward"} <= nodes_d, sorted(nodes_d)
+        errs_d = {n: _rel_norm(got_d[n], leaf.grad) for n, leaf in leaves.items()}
+        _report("backbone %s %dx%d D" % (name, H, W), errs_d)
+        for n, e in errs_d.items():
+            bound = BOUND_INPUT_PROJ if n.startswith("input_proj.") else BOUND_BACKBONE
+            assert e <= bound, (n, e, bound)
 
 
 # --------------------------------------------------------------------------------------------------------------- detector
@@ -178,8 +229,11 @@ def test_every_parameter_gradient_of_a_train_step_equals_float64(case):
     _, calibs, targets, _ = make_batch(B, "cuda", seed=5, resolution=(W, H))
     images = torch.zeros(B, 3, H, W, device="cuda")
 
-    def run(on, dtype):
-        with fused_switches(on):
+    def run(on, dtype, det=False):
+        with fused_switches(on), _mode(det), _msda_backward_calls() as calls:
+            if det:
+                from monosowa_amd import _lib, gemm_lt, pointwise
+                assert _lib.MSDA_DETERMINISTIC.sync() is True and pointwise.DETERMINISTIC.sync() is True and gemm_lt.DETERMINISTIC.sync() is True
             model = to_mi355x_layout(copy.deepcopy(model0).to(device="cuda", dtype=dtype)).train()
             leaves = [f.to(device="cuda", dtype=dtype).contiguous(memory_format=torch.channels_last).requires_grad_(True) for f in feats]
             model.backbone[0].body.feats = leaves
@@ -194,21 +248,39 @@ def test_every_parameter_gradient_of_a_train_step_equals_float64(case):
             grads.update({"feature.C%d" % (i + 3): f.grad for i, f in enumerate(leaves)})
             terms = {k: float(losses[k].detach()) for k in LOSS_KEYS}
             c.to(torch.float32)
-            return total.item(), terms, grads, nodes
+            return total.item(), terms, grads, nodes, dict(calls)
 
-    tF, lF, gF, nF = run(True, torch.float32)
-    tP, lP, gP, nP = run(False, torch.float32)
-    tR, lR, gR, nR = run(False, torch.float64)
-    print("\n%s: total F %.9g P %.9g R %.12g" % (case, tF, tP, tR))
+    tF, lF, gF, nF, cF = run(True, torch.float32)
+    tP, lP, gP, nP, _ = run(False, torch.float32)
+    tR, lR, gR, nR, _ = run(False, torch.float64)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    tD, lD, gD, nD, cD = run(True, torch.float32, det=True)
+    torch.cuda.synchronize()
+    seconds_d = time.perf_counter() - t0
+    tD2, lD2, gD2, _, _ = run(True, torch.float32, det=True)
+    print("\n%s: total F %.9g P %.9g D %.9g R %.12g" % (case, tF, tP, tD, tR))
+    print("D: %.2f s for model copy, forward and backward; MSDA backward calls F %s D %s" % (seconds_d, cF, cD))
     print("F nodes:", sorted(nF))
     print("P nodes:", sorted(nP))
+    # D: the fused operator's backward re-evaluated its prologue all six times (3 encoder layers, 3 decoder layers): the
+    # saved-prologue backward runs the row-tile scatter, which has no deterministic variant
+    assert cD == {"ms_deform_attn_fused_backward_merged": 6}, cD
+    assert sum(cF.values()) == 6, cF
+    # D twice: the same bits (the first repeatability check at the odd pyramid and with the encoder as block nodes)
+    assert tD == tD2 and lD == lD2 and set(gD) == set(gD2)
+    for n, g in gD.items():
+        assert (g is None and gD2[n] is None) or torch.equal(g, gD2[n]), "D: %s differs between two evaluations" % n
 
     loss_err = {k: abs(lF[k] - lR[k]) / max(abs(lR[k]), 1e-30) for k in LOSS_KEYS}
     loss_err_p = {k: abs(lP[k] - lR[k]) / max(abs(lR[k]), 1e-30) for k in LOSS_KEYS}
+    loss_err_d = {k: abs(lD[k] - lR[k]) / max(abs(lR[k]), 1e-30) for k in LOSS_KEYS}
     _report("loss terms F", loss_err)
     _report("loss terms P", loss_err_p)
+    _report("loss terms D", loss_err_d)
 
-    assert set(gF) == set(gR) == set(gP)
+    assert set(gF) == set(gR) == set(gP) == set(gD)
+    assert {n for n, g in gD.items() if g is None} == {n for n, g in gR.items() if g is None}
     none_f = {n for n, g in gF.items() if g is None}
     assert none_f == {n for n, g in gR.items() if g is None}, sorted(none_f ^ {n for n, g in gR.items() if g is None})
     assert none_f == {n for n, g in gP.items() if g is None}, sorted(none_f ^ {n for n, g in gP.items() if g is None})
@@ -219,21 +291,24 @@ def test_every_parameter_gradient_of_a_train_step_equals_float64(case):
     err = lambda g, n: float((g.double() - gR[n].double()).norm() / scale(n).double().norm().clamp_min(1e-300))
     eF = {n: err(gF[n], n) for n in gF if gR[n] is not None}
     eP = {n: err(gP[n], n) for n in gP if gR[n] is not None}
+    eD = {n: err(gD[n], n) for n in gD if gR[n] is not None}
     by_group = {}
     for n in eF:
         by_group.setdefault(_group(n), []).append(n)
     for (grp, bound), names in sorted(by_group.items()):
         _report("%s F (bound %.1e)" % (grp, bound), {n: eF[n] for n in names})
         _report("%s P" % grp, {n: eP[n] for n in names})
+        _report("%s D" % grp, {n: eD[n] for n in names})
     # F ran the fused nodes under test; P ran none of them
     fused = {"MSDeformAttnFusedMergedFunctionBackward", "_DDNLossBackward", "_DepthExpectationBackward", "_FocalClassificationBackward",
              "_HeadTailBackward", "_MatchedLossesBackward", "_MergedValueProjBackward", "_TokenLinearBackward", "_GroupNormNHWCBackward"}
     if B * sum(-(-H // s) * -(-W // s) for s in (8, 16, 32, 64)) >= 32768:
         fused |= {"_AttnBlockBackward", "_FFNBlockBackward"}
     assert fused <= nF, sorted(fused - nF)
+    assert fused <= nD, sorted(fused - nD)
     # (GroupNorm has no plain path; from 32,768 tokens on, token_linear splits the weight gradient whatever FAST_LINEAR says)
     assert not (fused - {"_GroupNormNHWCBackward", "_TokenLinearBackward"}) & nP, sorted(fused & nP)
     for k in LOSS_KEYS:
-        assert loss_err[k] <= BOUND_LOSS and loss_err_p[k] <= BOUND_LOSS, (k, loss_err[k], loss_err_p[k])
-    bad = [(n, eF[n], eP[n], b) for (_, b), names in by_group.items() for n in names if eF[n] > b or eP[n] > b]
-    assert not bad, "per-tensor ||g - g_ref|| / ||g_ref|| (name, F, P, bound): %s" % bad[:12]
+        assert loss_err[k] <= BOUND_LOSS and loss_err_p[k] <= BOUND_LOSS and loss_err_d[k] <= BOUND_LOSS, (k, loss_err[k], loss_err_p[k], loss_err_d[k])
+    bad = [(n, eF[n], eP[n], eD[n], b) for (_, b), names in by_group.items() for n in names if eF[n] > b or eP[n] > b or eD[n] > b]
+    assert not bad, "per-tensor ||g - g_ref|| / ||g_ref|| (name, F, P, D, bound): %s" % bad[:12]
