@@ -12,6 +12,7 @@ import numpy as np
 import torch
 import tqdm
 
+from ..image_prep import is_raw_batch, prepare
 from .decode_helper import PinholeCalib, decode_detections, extract_dets_from_outputs
 from .save_helper import unwrap, load_checkpoint
 
@@ -82,7 +83,10 @@ class Tester(object):
         results, model_time, n_img = {}, 0.0, 0
         bar = tqdm.tqdm(total=len(self.dataloader), leave=True, desc="Evaluation Progress")
         for inputs, calibs, targets, info in self.dataloader:
-            inputs = inputs.to(self.device)
+            if is_raw_batch(inputs):                                  # dataset.device_aug: one launch prepares the batch
+                inputs = prepare(inputs, info["prep"], self.device)
+            else:
+                inputs = inputs.to(self.device)
             calibs_dev = calibs.to(self.device)
             img_sizes = info["img_size"].to(self.device).clone()
             img_sizes[:, 1] = img_sizes[:, 1] / info["height_crop"].to(self.device)

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 import tqdm
 
+from ..image_prep import is_raw_batch, prepare
 from ..monodetr import misc
 from ..monodetr.criterion import weighted_total
 from ..synthetic import attach_host_mask
@@ -51,11 +52,15 @@ def stage_batch(raw, device):
     """One collated loader batch ``(inputs, calibs, targets, info)`` onto ``device`` (reference: trainer_helper.py:121-127, a
     per-key ``.to(device)``): non-blocking copies (pinned source buffers when the loader pins), images to channels-last for the
     MIOpen NHWC kernels, and the object mask kept on the host next to its device copy so that ``prepare_targets`` needs no
-    device -> host synchronisation."""
+    device -> host synchronisation.  A raw batch (dataset.device_aug: uint8 images on one canvas, records in ``info["prep"]``) is
+    copied as it is and becomes the same float32 channels-last images through one launch of monosowa_amd/image_prep.py."""
     inputs, calibs, targets, info = raw
-    inputs = inputs.to(device, non_blocking=True)
-    if inputs.is_cuda:
-        inputs = inputs.contiguous(memory_format=torch.channels_last)
+    if is_raw_batch(inputs):
+        inputs = prepare(inputs, info["prep"], device)
+    else:
+        inputs = inputs.to(device, non_blocking=True)
+        if inputs.is_cuda:
+            inputs = inputs.contiguous(memory_format=torch.channels_last)
     calibs = calibs.to(device, non_blocking=True)
     host_mask = targets["mask_2d"].numpy() if not targets["mask_2d"].is_cuda else None
     targets = {k: v.to(device, non_blocking=True) for k, v in targets.items()}

@@ -12,6 +12,11 @@ what the converters k360_to_k.py / waymo_to_kitti_projected.py write.
 `aug_pd` (photometric distortion, lib/datasets/kitti/pd.py:114-416, ON in the reference's shipped mixed-dataset config
 checkpoints/best_kitti_k360_to_kitti/monodetr_kk360_05.yaml:18): monosowa_amd/photometric.py.
 
+`device_aug` (optional, default False; this project's, not the reference's): __getitem__ returns the decoded RGB uint8 image
+`[h, w, 3]` in place of the prepared one and adds the parameter record `info["prep"]` (size, `trans_inv`, flip, photometric
+draws); the same draws are consumed from `np.random`, every other output is identical, and monosowa_amd/image_prep.py turns
+a batch of them into the same float32 images with one HIP launch.
+
 Not carried over (off in both shipped configs and tied to files of the pseudo-label pipeline): `use_add_data` (per-car
 masks / lidar in dill+zstd), `use_depth`, `output_lidar` -- they raise.
 """
@@ -191,6 +196,7 @@ class KITTI_Dataset(data.Dataset):
                                           "and is off in both shipped configs" % key)
         self.aug_pd = cfg.get("aug_pd", False)                       # on in checkpoints/.../monodetr_kk360_05.yaml:18
         self.pd = PhotometricDistort()
+        self.device_aug = bool(cfg.get("device_aug", False))         # raw image + record out; the pixels are image_prep.prepare's
         assert split in ["train", "val", "trainval", "test"]
         with open(os.path.join(self.root_dir, "ImageSets", split + ".txt")) as f:
             self.idx_list = [x.strip() for x in f.readlines()]
@@ -222,6 +228,13 @@ class KITTI_Dataset(data.Dataset):
     def get_image(self, idx):
         return Image.open(os.path.join(self.image_dir, "%06d.png" % idx))
 
+    def get_raw_image(self, img, idx):
+        """The decoded image as the uint8 [h, w, 3] array the device path reads (device_aug)."""
+        if img.mode != "RGB":
+            raise ValueError("%s is not an 8-bit RGB image (PIL mode %r): dataset.device_aug prepares 8-bit RGB only"
+                             % (os.path.join(self.image_dir, "%06d.png" % idx), img.mode))
+        return np.array(img)
+
     def get_label(self, idx):
         return get_objects_from_label(os.path.join(self.label_dir, "%06d.txt" % idx))
 
@@ -251,26 +264,36 @@ class KITTI_Dataset(data.Dataset):
         center = np.array(img_size) / 2
         crop_size, crop_scale = img_size, 1
         flipped = False
+        raw, pd_record = (self.get_raw_image(img, index), None) if self.device_aug else (None, None)
         if self.data_augmentation:                                   # draw order of the reference: [photometric], flip, crop?, scale, shift x, shift y
-            if self.aug_pd:                                          # kitti_dataset.py:182-185
+            if self.aug_pd and self.device_aug:
+                pd_record = self.pd.draw()                           # the same draws; applied on the device
+            elif self.aug_pd:                                        # kitti_dataset.py:182-185
                 img = Image.fromarray(self.pd(np.array(img).astype(np.float32)).astype(np.uint8))
             if np.random.random() < self.random_flip:
                 flipped = True
-                img = img.transpose(Image.FLIP_LEFT_RIGHT)
+                if not self.device_aug:
+                    img = img.transpose(Image.FLIP_LEFT_RIGHT)
             if self.aug_crop and np.random.random() < self.random_crop:
                 crop_scale = np.clip(np.random.randn() * self.scale + 1, 1 - self.scale, 1 + self.scale)
                 crop_size = img_size * crop_scale
                 center[0] += img_size[0] * np.clip(np.random.randn() * self.shift, -2 * self.shift, 2 * self.shift)
                 center[1] += img_size[1] * np.clip(np.random.randn() * self.shift, -2 * self.shift, 2 * self.shift)
         trans, trans_inv = get_affine_transform(center, crop_size, 0, self.resolution, inv=1)
-        img = img.transform(tuple(self.resolution.tolist()), method=Image.AFFINE, data=tuple(trans_inv.reshape(-1).tolist()),
-                            resample=Image.BILINEAR)
-        img = ((np.array(img).astype(np.float32) / 255.0 - self.mean) / self.std).transpose(2, 0, 1)
+        if self.device_aug:
+            from .image_prep import make_record
+            img = raw
+        else:
+            img = img.transform(tuple(self.resolution.tolist()), method=Image.AFFINE, data=tuple(trans_inv.reshape(-1).tolist()),
+                                resample=Image.BILINEAR)
+            img = ((np.array(img).astype(np.float32) / 255.0 - self.mean) / self.std).transpose(2, 0, 1)
         fu, fv, cu, cv, height_cropped = self.adjust_intrinsics(calib.fu, calib.fv, calib.cu, calib.cv, img_size, center, crop_scale,
                                                                  crop_size, flipped)
         canonical_scale = self.canonical_focal_length / fu if self.use_canonical_module else 1.0
         info = {"img_id": index, "img_size": img_size, "bbox_downsample_ratio": img_size / features_size,
                 "canonical_scale": canonical_scale, "height_crop": height_cropped}
+        if self.device_aug:
+            info["prep"] = make_record(img_size, trans_inv, flipped, pd_record)
         if self.split == "test":
             return img, calib.P2, img, info
 

@@ -70,29 +70,55 @@ class PhotometricDistort:
         self.saturation = saturation
         self.hue_delta = hue_delta
 
-    def _contrast(self, im):
-        if np.random.randint(2):
-            im *= np.random.uniform(*self.contrast)
+    def _draw_contrast(self):
+        return float(np.random.uniform(*self.contrast)) if np.random.randint(2) else None
+
+    def draw(self):
+        """The parameter record of one image, consuming ``numpy.random`` exactly as ``__call__`` always has (the module docstring's
+        draw order): a dict whose ``None`` entries are the steps whose draw said "skip"."""
+        rnd = np.random
+        rec = {"brightness": float(rnd.uniform(-self.brightness_delta, self.brightness_delta)) if rnd.randint(2) else None}   # pd.py:189-200
+        rec["contrast_first"] = bool(rnd.randint(2))
+        if rec["contrast_first"]:
+            rec["contrast"] = self._draw_contrast()
+        rec["saturation"] = float(rnd.uniform(*self.saturation)) if rnd.randint(2) else None                                 # pd.py:114-126
+        rec["hue"] = float(rnd.uniform(-self.hue_delta, self.hue_delta)) if rnd.randint(2) else None                         # pd.py:129-140
+        if not rec["contrast_first"]:
+            rec["contrast"] = self._draw_contrast()
+        rec["perm"] = _PERMS[rnd.randint(len(_PERMS))] if rnd.randint(2) else None                                           # pd.py:143-154
+        return rec
+
+    @staticmethod
+    def apply(image, rec):
+        """The drawn record applied to ``image`` (float32 [..., 3], not modified).  Every parameter enters as ``float32(draw)``: numpy
+        adds and multiplies a float32 image by a Python float in float32.  A skipped step is skipped, not run with a neutral
+        parameter; the HSV round trip always runs and is not an identity (negative pixels)."""
+        im = np.array(image, dtype=np.float32)
+        contrast = None if rec["contrast"] is None else np.float32(rec["contrast"])
+        if rec["brightness"] is not None:
+            im += np.float32(rec["brightness"])
+        if rec["contrast_first"] and contrast is not None:
+            im *= contrast
+        im = bgr_to_hsv(im)
+        if rec["saturation"] is not None:
+            im[..., 1] *= np.float32(rec["saturation"])
+        if rec["hue"] is not None:
+            im[..., 0] += np.float32(rec["hue"])
+            im[..., 0][im[..., 0] > 360.0] -= 360.0
+            im[..., 0][im[..., 0] < 0.0] += 360.0
+        im = hsv_to_bgr(im)
+        if not rec["contrast_first"] and contrast is not None:
+            im *= contrast
+        if rec["perm"] is not None:
+            im = im[..., rec["perm"]]
         return im
 
     def __call__(self, image):
-        rnd = np.random
-        im = image.copy()
-        if rnd.randint(2):                                               # RandomBrightness (pd.py:189-200)
-            im += rnd.uniform(-self.brightness_delta, self.brightness_delta)
-        contrast_first = bool(rnd.randint(2))
-        if contrast_first:
-            im = self._contrast(im)
-        im = bgr_to_hsv(im)
-        if rnd.randint(2):                                               # RandomSaturation (pd.py:114-126)
-            im[:, :, 1] *= rnd.uniform(*self.saturation)
-        if rnd.randint(2):                                               # RandomHue (pd.py:129-140)
-            im[:, :, 0] += rnd.uniform(-self.hue_delta, self.hue_delta)
-            im[:, :, 0][im[:, :, 0] > 360.0] -= 360.0
-            im[:, :, 0][im[:, :, 0] < 0.0] += 360.0
-        im = hsv_to_bgr(im)
-        if not contrast_first:
-            im = self._contrast(im)
-        if rnd.randint(2):                                               # RandomLightingNoise (pd.py:143-154)
-            im = im[:, :, _PERMS[rnd.randint(len(_PERMS))]]
-        return im
+        return self.apply(image, self.draw())
+
+
+def wrap_to_uint8(im):
+    """What ``astype(np.uint8)`` does to a float32 image on x86-64 (the loader's cast, kitti_dataset.py), stated without the
+    platform: truncation toward zero, then the low eight bits -- negative and over-range values WRAP, they do not saturate.
+    Presumes every value inside the int32 range."""
+    return (np.trunc(np.asarray(im, dtype=np.float64)).astype(np.int64) & 255).astype(np.uint8)
