@@ -28,6 +28,15 @@ int mono_box3d_overlap_f32(const float *boxes, const float *query, float *out, l
 int mono_extract_dets_f32(const float *logits, const float *boxes, const float *angle, const float *size3d, const float *depth,
                           float *out, int B, int Q, int C, int K, void *stream);
 
+/* KITTI rows of the detections (the public Detector's decode): lib/helpers/decode_helper.py:8-55 `decode_detections` as one
+ * kernel in double, numpy's promotions kept (float32 detections widened; the threshold compared in float32; the final score a
+ * float32 product, widened; `//` for the padding; arg-max ties to the lowest index).
+ * dets [B, K, 37] (mono_extract_dets_f32's rows), geom f64 [B, 10] = (img_w, img_h, height_crop, canonical_scale, cu, cv, fu,
+ * fv, tx, ty), cls_mean_size f64 [C, 3] -> rows f64 [B, K, 14] = (cls, alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry, score):
+ * the rows with ~(score < threshold) compacted in rank order, the rest zero; count int32 [B].  K <= 4096. */
+int mono_decode_dets_f64(const float *dets, const double *geom, const double *cls_mean_size, double threshold, double *rows,
+                         int *count, int B, int K, int C, void *stream);
+
 /* KITTI AP accumulation, HOST functions: the official matching protocol as kitti_eval_python/eval.py:234-410
  * runs it (numba there), one call per (class, difficulty, min_overlap) over all images.  Host pointers.
  *   n_gt / n_dt / n_dc [n_images]: boxes per image;   overlaps: the images' [n_dt, n_gt] matrices (row = detection), concatenated;

@@ -1,3 +1,10 @@
 """MI355X-native MonoDETR forward/backward path for MonoSOWA (gfx950 HIP kernels behind the
 reference's MultiScaleDeformableAttention operator boundary)."""
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    if name == "Detector":                  # the public inference API (monosowa_amd/detector.py); imported on first use
+        from .detector import Detector
+        return Detector
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

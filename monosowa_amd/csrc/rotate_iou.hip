@@ -198,6 +198,110 @@ __global__ __launch_bounds__(kThreads) void extract_dets_kernel(
   }
 }
 
+// ---- KITTI rows from detections: lib/helpers/decode_helper.py:8-55 (decode_detections) as ONE kernel, in double ----
+// dets f32 [B, K, 37] + per-image geometry f64 [B, 10] = (img_w, img_h, height_crop, canonical_scale, cu, cv, fu, fv, tx, ty)
+// -> rows f64 [B, K, 14] = (cls, alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry, score), the rows with ~(score < threshold)
+// compacted in rank order, the rest zero; count [B].  Every step is numpy's own expression with numpy's promotions: float32
+// detections widen into float64 arithmetic, each product and sum is rounded on its own (no fused multiply-add), the
+// threshold is compared in float32, the final score is a float32 product widened, `//` is numpy's floor division, arg-max
+// takes the lowest index of the largest value (the first NaN, as numpy does).  Only ry goes through a library function
+// (atan2).  One workgroup per image; a detection per thread.
+constexpr int kDecodeThreads = 256;
+constexpr int kDecodeMaxK = 4096;        // detections per image the kernel accepts (a 4 KB flag array in LDS)
+constexpr int kGeomDoubles = 10;
+constexpr int kRowDoubles = 14;
+
+__device__ __forceinline__ double floor_divide(double a, double b) {        // numpy's npy_floor_divide for doubles
+#pragma clang fp contract(off)
+  if (b == 0.0) return a / b;
+  const double mod = fmod(a, b);
+  double div = (a - mod) / b;
+  if (mod != 0.0 && ((b < 0.0) != (mod < 0.0))) div -= 1.0;
+  if (div != 0.0) {
+    double fl = floor(div);
+    if (div - fl > 0.5) fl += 1.0;
+    return fl;
+  }
+  return copysign(0.0, a / b);
+}
+
+__global__ __launch_bounds__(kDecodeThreads) void decode_dets_kernel(
+    const float *__restrict__ dets, const double *__restrict__ geom, const double *__restrict__ cls_mean_size, float threshold,
+    double *__restrict__ rows, int *__restrict__ count, int K, int C) {
+#pragma clang fp contract(off)
+  __shared__ unsigned char kept[kDecodeMaxK];
+  const int b = blockIdx.x;
+  const float *db = dets + (long long)b * K * 37;
+  for (int j = threadIdx.x; j < K; j += kDecodeThreads) kept[j] = !(db[j * 37 + 1] < threshold);
+  __syncthreads();
+  int total = 0;
+  for (int j = 0; j < K; ++j) total += kept[j];
+  if (threadIdx.x == 0) count[b] = total;
+  const double *g = geom + (long long)b * kGeomDoubles;
+  const double img_w = g[0], img_h = g[1], cu = g[4], cv = g[5], fu = g[6], fv = g[7], tx = g[8], ty = g[9];
+  const double crop_h = img_h / g[2];
+  const double padding = floor_divide(img_h - crop_h, 2.0);
+  const double kPi = 3.141592653589793, kTwoPi = 2 * kPi, kBin = kTwoPi / 12.0;
+  double *rb = rows + (long long)b * K * kRowDoubles;
+  for (int j = threadIdx.x; j < K; j += kDecodeThreads) {
+    if (j >= total) {                                        // the tail behind the kept rows
+      double *z = rb + (long long)j * kRowDoubles;
+      for (int c = 0; c < kRowDoubles; ++c) z[c] = 0.0;
+    }
+    if (!kept[j]) continue;
+    int pos = 0;
+    for (int i = 0; i < j; ++i) pos += kept[i];
+    const float *d = db + j * 37;
+    const int cls = (int)(long long)d[0];
+    const int cm = cls < 0 ? 0 : (cls >= C ? C - 1 : cls);   // (numpy raises on a class outside the table; never read outside it)
+    const double x = (double)d[2] * img_w;
+    const double y = (double)d[3] * crop_h + padding;
+    const double w = (double)d[4] * img_w;
+    const double h = (double)d[5] * crop_h;
+    const double depth = (double)d[6] / g[3];
+    const double dim0 = (double)d[31] + cls_mean_size[cm * 3 + 0];
+    const double dim1 = (double)d[32] + cls_mean_size[cm * 3 + 1];
+    const double dim2 = (double)d[33] + cls_mean_size[cm * 3 + 2];
+    const double x3d = (double)d[34] * img_w;
+    const double y3d = (double)d[35] * crop_h + padding;
+    const double loc_x = ((x3d - cu) * depth) / fu + tx;
+    const double loc_y = ((y3d - cv) * depth) / fv + ty + dim0 / 2;
+    int bin = 0;
+    float best = d[7];
+    if (!(best != best)) {
+      for (int k = 1; k < 12; ++k) {
+        const float v = d[7 + k];
+        if (!(v <= best)) {
+          best = v;
+          bin = k;
+          if (v != v) break;
+        }
+      }
+    }
+    double alpha = (double)bin * kBin + (double)d[19 + bin];
+    alpha = alpha > kPi ? alpha - kTwoPi : alpha;
+    double ry = alpha + atan2(x - cu, fu);
+    ry = ry > kPi ? ry - kTwoPi : ry;
+    ry = ry < -kPi ? ry + kTwoPi : ry;
+    const float final_score = d[1] * d[36];
+    double *o = rb + (long long)pos * kRowDoubles;
+    o[0] = (double)cls;
+    o[1] = alpha;
+    o[2] = x - w / 2;
+    o[3] = y - h / 2;
+    o[4] = x + w / 2;
+    o[5] = y + h / 2;
+    o[6] = dim0;
+    o[7] = dim1;
+    o[8] = dim2;
+    o[9] = loc_x;
+    o[10] = loc_y;
+    o[11] = depth;
+    o[12] = ry;
+    o[13] = (double)final_score;
+  }
+}
+
 }  // namespace dets
 
 extern "C" {
@@ -207,6 +311,15 @@ int mono_extract_dets_f32(const float *logits, const float *boxes, const float *
   if (!logits || !boxes || !angle || !size3d || !depth || !out) return -1;
   if (B <= 0 || Q <= 0 || C <= 0 || K <= 0 || K > Q * C || (long long)Q * C > dets::kMaxScores) return -2;
   dets::extract_dets_kernel<<<B, dets::kThreads, 0, (hipStream_t)stream_>>>(logits, boxes, angle, size3d, depth, out, Q, C, K);
+  return (int)hipGetLastError();
+}
+
+int mono_decode_dets_f64(const float *dets, const double *geom, const double *cls_mean_size, double threshold, double *rows,
+                         int *count, int B, int K, int C, void *stream_) {
+  if (!dets || !geom || !cls_mean_size || !rows || !count) return -1;
+  if (B <= 0 || K <= 0 || C <= 0 || K > dets::kDecodeMaxK) return -2;
+  dets::decode_dets_kernel<<<B, dets::kDecodeThreads, 0, (hipStream_t)stream_>>>(dets, geom, cls_mean_size, (float)threshold, rows,
+                                                                                count, K, C);
   return (int)hipGetLastError();
 }
 

@@ -1,19 +1,18 @@
 """Inference loop and KITTI result writer (reference: lib/helpers/tester_helper.py -- ``Tester``
 :14-28, ``test`` :28-78, ``inference`` :80-166, ``save_results`` :168-188, ``evaluate`` :190-194).
 
-Model time is measured with device synchronisation (the reference's ``time.time()`` pair at :94-99
-brackets an asynchronous launch).  Open3D visualisation (:196-258) is out of scope; KITTI AP
+The per-batch work runs on monosowa_amd/inference.py's ``InferenceEngine``; model time is measured with device events around
+each forward (the reference's ``time.time()`` pair at :94-99 brackets an asynchronous launch).  Open3D visualisation (:196-258) is out of scope; KITTI AP
 evaluation is delegated to ``dataset.eval`` when the dataset provides it."""
 import glob
 import os
-import time
 
 import numpy as np
 import torch
 import tqdm
 
-from ..image_prep import is_raw_batch, prepare
-from .decode_helper import PinholeCalib, decode_detections, extract_dets_from_outputs
+from ..image_prep import is_raw_batch
+from .decode_helper import PinholeCalib, decode_detections
 from .save_helper import unwrap, load_checkpoint
 
 
@@ -79,53 +78,45 @@ class Tester(object):
 
     @torch.no_grad()
     def inference(self):
+        """One pass over the loader on an ``InferenceEngine`` (graph replay, no device-wide synchronisation per batch): batches
+        are submitted as the loader yields them and decoded here as they complete, in order, while the next ones run."""
+        from ..inference import InferenceEngine
         self.model.eval()
-        results, model_time, n_img = {}, 0.0, 0
+        results = {}
+        dataset = self.dataloader.dataset
+        threshold = self.cfg.get("threshold", 0.2)
+
+        def consume(batches):
+            for done in batches:
+                calibs, info = done.tag
+                if hasattr(dataset, "get_calib"):
+                    cal = [dataset.get_calib(int(i)) for i in info["img_id"]]
+                else:
+                    cal = [PinholeCalib(p) for p in calibs.numpy()]
+                info_np = {k: (v.numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in info.items()}
+                results.update(decode_detections(dets=done.dets, info=info_np, calibs=cal, cls_mean_size=dataset.cls_mean_size,
+                                                 threshold=threshold))
+
+        engine = InferenceEngine(self.model, self.device, topk=self.cfg["topk"], max_objs=self.max_objs)
         bar = tqdm.tqdm(total=len(self.dataloader), leave=True, desc="Evaluation Progress")
-        for inputs, calibs, targets, info in self.dataloader:
-            if is_raw_batch(inputs):                                  # dataset.device_aug: one launch prepares the batch
-                inputs = prepare(inputs, info["prep"], self.device)
-            else:
-                inputs = inputs.to(self.device)
-            calibs_dev = calibs.to(self.device)
-            img_sizes = info["img_size"].to(self.device).clone()
-            img_sizes[:, 1] = img_sizes[:, 1] / info["height_crop"].to(self.device)
-            if self.device.type == "cuda":
-                torch.cuda.synchronize()
-            t0 = time.time()
-            outputs = self.model(inputs, calibs_dev, targets, img_sizes, dn_args=0)
-            if self.device.type == "cuda":
-                torch.cuda.synchronize()
-            model_time += time.time() - t0
-            n_img += inputs.shape[0]
-            dets = extract_dets_from_outputs(outputs=outputs, K=self.max_objs, topk=self.cfg["topk"]).cpu().numpy()
-            dataset = self.dataloader.dataset
-            if hasattr(dataset, "get_calib"):
-                cal = [dataset.get_calib(int(i)) for i in info["img_id"]]
-            else:
-                cal = [PinholeCalib(p) for p in calibs.numpy()]
-            info_np = {k: (v.numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in info.items()}
-            results.update(decode_detections(dets=dets, info=info_np, calibs=cal, cls_mean_size=dataset.cls_mean_size,
-                                             threshold=self.cfg.get("threshold", 0.2)))
-            bar.update()
+        try:
+            for inputs, calibs, targets, info in self.dataloader:
+                consume(engine.submit(inputs, calibs, info["img_size"], info["height_crop"],
+                                      prep=info["prep"] if is_raw_batch(inputs) else None, tag=(calibs, info)))
+                bar.update()
+            consume(engine.drain())
+        finally:
+            engine.close()                                            # the graphs and their pools: every pass captures current weights
         bar.close()
-        self.last_img_per_s = n_img / max(model_time, 1e-9)
+        n_img = engine.images
+        self.last_img_per_s = n_img / max(engine.model_seconds, 1e-9)
         print("inference on {} images: {:.2f} img/s (model only)".format(n_img, self.last_img_per_s))
         self.logger.info("==> Saving ...")
         self.save_results(results)
         return results
 
     def save_results(self, results):
-        """One KITTI label file per image: 'Class 0.0 0 alpha x1 y1 x2 y2 h w l x y z ry score', '%.2f'."""
-        output_dir = os.path.join(self.output_dir, "outputs", "data")
-        os.makedirs(output_dir, exist_ok=True)
-        for img_id, preds in results.items():
-            with open(os.path.join(output_dir, "{:06d}.txt".format(int(img_id))), "w") as f:
-                for p in preds:
-                    f.write("{} 0.0 0".format(self.class_name[int(p[0])]))
-                    for j in range(1, len(p)):
-                        f.write(" {:.2f}".format(p[j]))
-                    f.write("\n")
+        write_kitti_results(results, self.class_name, os.path.join(self.output_dir, "outputs", "data"))
 
     def evaluate(self):
         results_dir = os.path.join(self.output_dir, "outputs", "data")
@@ -138,6 +129,18 @@ class Tester(object):
                                           getattr(dataset, "writelist", ["Car"]), self.logger)
         self.logger.info("dataset has no ground-truth label directory: nothing to evaluate; returning 0")
         return 0.0
+
+
+def write_kitti_results(results, class_name, output_dir):
+    """One KITTI label file per image: 'Class 0.0 0 alpha x1 y1 x2 y2 h w l x y z ry score', '%.2f'."""
+    os.makedirs(output_dir, exist_ok=True)
+    for img_id, preds in results.items():
+        with open(os.path.join(output_dir, "{:06d}.txt".format(int(img_id))), "w") as f:
+            for p in preds:
+                f.write("{} 0.0 0".format(class_name[int(p[0])]))
+                for j in range(1, len(p)):
+                    f.write(" {:.2f}".format(p[j]))
+                f.write("\n")
 
 
 def evaluate_kitti_results(results_dir, label_dir, img_ids, categories, logger):

@@ -7,7 +7,7 @@ batch, bit for bit equal to what ``KITTI_Dataset.__getitem__`` computes on the C
     make_record(size, trans_inv, flipped, pd)   one image's parameter record, float64 [RECORD_DOUBLES]  (info["prep"])
     collate_raw(samples)                        pads the raw uint8 images of a batch to one canvas, default-collates the rest
     is_raw_batch(inputs)                        a collated raw batch (uint8 [B, Hc, Wc, 3]) rather than prepared images
-    prepare(raw, records, device)               -> float32 [B, 3, H, W], channels-last on the GPU (what stage_batch produces)
+    prepare(raw, records, device, out=None)     -> float32 [B, 3, H, W], channels-last on the GPU (what stage_batch produces)
     prepare_reference(raw, records)             the same in numpy: float64 coordinates and PIL's rules, photometric.py's float32
 
 ``prepare`` on a CPU device IS ``prepare_reference``; on a GPU a missing library is an error, never a fall-back.
@@ -171,13 +171,22 @@ def _device_lut(device, mean, std):
     return _LUTS[key]
 
 
-def prepare(raw, records, device, resolution=RESOLUTION, mean=MEAN, std=STD):
+def prepare(raw, records, device, resolution=RESOLUTION, mean=MEAN, std=STD, out=None):
     """raw uint8 ``[B, Hc, Wc, 3]`` and records float64 ``[B, RECORD_DOUBLES]`` (host tensors, pinned or not, or already on
     ``device``) -> the float32 batch ``[B, 3, H, W]`` on ``device``: channels-last from one launch of the library on the
-    current stream after non-blocking copies, with no device -> host synchronisation; on a CPU device, ``prepare_reference``."""
+    current stream after non-blocking copies, with no device -> host synchronisation; on a CPU device, ``prepare_reference``.
+    ``out``: a float32 ``[B, 3, H, W]`` tensor on ``device`` (channels-last on a GPU) to write into instead of allocating -- the
+    static input of a captured graph; it is returned."""
     device = torch.device(device)
+    if out is not None:
+        want = (raw.shape[0], 3, resolution[1], resolution[0])
+        if out.dtype != torch.float32 or tuple(out.shape) != want or out.device.type != device.type \
+                or (device.type == "cuda" and not out.is_contiguous(memory_format=torch.channels_last)):
+            raise ValueError("out must be a float32 %s tensor on %s (channels-last on a GPU), got %s %s on %s"
+                             % (want, device, out.dtype, tuple(out.shape), out.device))
     if device.type != "cuda":
-        return torch.from_numpy(prepare_reference(raw, records, resolution, mean, std))
+        res = torch.from_numpy(prepare_reference(raw, records, resolution, mean, std))
+        return res if out is None else out.copy_(res)
     _check(raw, records)
     if resolution[0] % 4:
         raise ValueError("the output width must be a multiple of 4, got %d" % resolution[0])
@@ -187,7 +196,8 @@ def prepare(raw, records, device, resolution=RESOLUTION, mean=MEAN, std=STD):
         lut = _device_lut(torch.device("cuda", torch.cuda.current_device()), mean, std)
         raw = raw.to(device, non_blocking=True).contiguous()
         records = records.to(device, non_blocking=True).contiguous()
-        out = torch.empty((B, 3, resolution[1], resolution[0]), dtype=torch.float32, device=device, memory_format=torch.channels_last)
+        if out is None:
+            out = torch.empty((B, 3, resolution[1], resolution[0]), dtype=torch.float32, device=device, memory_format=torch.channels_last)
         code = load().mono_image_prep_f32(raw.data_ptr(), records.data_ptr(), lut.data_ptr(), out.data_ptr(), B, Hc, Wc,
                                           resolution[1], resolution[0], raw_stream())
     if code:

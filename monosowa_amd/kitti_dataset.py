@@ -177,6 +177,27 @@ class KITTI_Dataset(data.Dataset):
     def __init__(self, split, cfg):
         self.root_dir = cfg.get("root_dir")
         self.split = split
+        assert split in ["train", "val", "trainval", "test"]
+        self._settings(cfg)
+        with open(os.path.join(self.root_dir, "ImageSets", split + ".txt")) as f:
+            self.idx_list = [x.strip() for x in f.readlines()]
+        self.data_dir = os.path.join(self.root_dir, "testing" if split == "test" else "training")
+        self.image_dir = os.path.join(self.data_dir, "image_2")
+        self.calib_dir = os.path.join(self.data_dir, "calib")
+        self.label_dir = os.path.join(self.data_dir, "label_2")
+        self.data_augmentation = split in ["train", "trainval"]
+
+    @classmethod
+    def settings(cls, cfg):
+        """The dataset's settings alone -- class names, ``cls_mean_size``, resolution, canonical focal length, ``adjust_intrinsics`` --
+        as an instance without a directory behind it (monosowa_amd/detector.py: frames that come from no KITTI directory)."""
+        self = cls.__new__(cls)
+        self.root_dir = self.split = None
+        self.data_augmentation = False
+        self._settings(cfg)
+        return self
+
+    def _settings(self, cfg):
         self.num_classes, self.max_objs = 3, 50
         self.class_name = ["Pedestrian", "Car", "Cyclist"]
         self.cls2id = {"Pedestrian": 0, "Car": 1, "Cyclist": 2}
@@ -197,14 +218,6 @@ class KITTI_Dataset(data.Dataset):
         self.aug_pd = cfg.get("aug_pd", False)                       # on in checkpoints/.../monodetr_kk360_05.yaml:18
         self.pd = PhotometricDistort()
         self.device_aug = bool(cfg.get("device_aug", False))         # raw image + record out; the pixels are image_prep.prepare's
-        assert split in ["train", "val", "trainval", "test"]
-        with open(os.path.join(self.root_dir, "ImageSets", split + ".txt")) as f:
-            self.idx_list = [x.strip() for x in f.readlines()]
-        self.data_dir = os.path.join(self.root_dir, "testing" if split == "test" else "training")
-        self.image_dir = os.path.join(self.data_dir, "image_2")
-        self.calib_dir = os.path.join(self.data_dir, "calib")
-        self.label_dir = os.path.join(self.data_dir, "label_2")
-        self.data_augmentation = split in ["train", "trainval"]
         self.aug_crop, self.aug_calib = cfg.get("aug_crop", False), cfg.get("aug_calib", False)
         self.random_flip, self.random_crop = cfg.get("random_flip", 0.5), cfg.get("random_crop", 0.5)
         self.scale, self.shift = cfg.get("scale", 0.4), cfg.get("shift", 0.1)

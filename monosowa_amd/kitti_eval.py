@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 _PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmonosowa_kitti.so")
-SYMBOLS = ("mono_rotate_iou_f32", "mono_box3d_overlap_f32", "mono_extract_dets_f32", "mono_kitti_tp_scores_f64", "mono_kitti_pr_f64")
+SYMBOLS = ("mono_rotate_iou_f32", "mono_box3d_overlap_f32", "mono_extract_dets_f32", "mono_decode_dets_f64", "mono_kitti_tp_scores_f64", "mono_kitti_pr_f64")
 _lib = None
 
 
@@ -39,6 +39,8 @@ def load():
         lib.mono_extract_dets_f32.restype = I
         lib.mono_extract_dets_f32.argtypes = [P] * 6 + [I] * 4 + [P]
         D = ctypes.c_double
+        lib.mono_decode_dets_f64.restype = I
+        lib.mono_decode_dets_f64.argtypes = [P] * 3 + [D, P, P] + [I] * 3 + [P]
         lib.mono_kitti_tp_scores_f64.restype = I
         lib.mono_kitti_tp_scores_f64.argtypes = [LL] + [P] * 9 + [I, D, P, P]
         lib.mono_kitti_pr_f64.restype = I
@@ -93,6 +95,32 @@ def extract_dets_device(outputs, topk=50):
     if code:
         raise RuntimeError("mono_extract_dets_f32 failed with code %d" % code)
     return out
+
+
+GEOM_DOUBLES = 10         # per image: img_w, img_h, height_crop, canonical_scale, cu, cv, fu, fv, tx, ty (monosowa_kitti.h)
+
+
+def decode_dets_device(dets, geom, cls_mean_size, threshold, rows=None, count=None):
+    """decode_helper.py:8-55 (``decode_detections``) in one launch on the current stream: detections float32 ``[B, K, 37]``,
+    per-image geometry float64 ``[B, GEOM_DOUBLES]`` and ``cls_mean_size`` float64 ``[C, 3]`` (CUDA tensors) -> rows float64
+    ``[B, K, 14]`` (kept rows first, in rank order, the rest zero) and count int32 ``[B]``."""
+    B, K, width = dets.shape
+    if width != 37 or dets.dtype != torch.float32 or not dets.is_cuda or not dets.is_contiguous():
+        raise ValueError("detections must be a contiguous float32 CUDA tensor [B, K, 37], got %s %s" % (dets.dtype, tuple(dets.shape)))
+    for name, t, shape in (("geom", geom, (B, GEOM_DOUBLES)), ("cls_mean_size", cls_mean_size, (cls_mean_size.shape[0], 3))):
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != dets.device or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float64 tensor %s on %s, got %s %s on %s"
+                             % (name, shape, dets.device, t.dtype, tuple(t.shape), t.device))
+    if rows is None:
+        rows = torch.empty((B, K, 14), dtype=torch.float64, device=dets.device)
+    if count is None:
+        count = torch.empty((B,), dtype=torch.int32, device=dets.device)
+    with torch.cuda.device(dets.device):
+        code = load().mono_decode_dets_f64(dets.data_ptr(), geom.data_ptr(), cls_mean_size.data_ptr(), float(threshold), rows.data_ptr(),
+                                           count.data_ptr(), B, K, int(cls_mean_size.shape[0]), torch.cuda.current_stream().cuda_stream)
+    if code:
+        raise RuntimeError("mono_decode_dets_f64 failed with code %d" % code)
+    return rows, count
 
 
 # ================================================================================================ AP accumulation
