@@ -289,19 +289,30 @@ __global__ __launch_bounds__(256, ATTN_BWD_WAVES) void bwd_dq_kernel(const Args 
   const float *qp = a.q + b * a.sq.b + hd * a.sq.h + (long long)qc * a.sq.t + 16 * h;
   const float *dop = a.dout + b * a.so.b + hd * a.so.h + (long long)qc * a.so.t + 16 * h;
   // delta[q] = sum_d dO[q][d] O[q][d] is evaluated here (the lane holds its half of the dO row anyway) and left in Args::delta
-  // for bwd_dkdv, which runs behind this kernel on the same stream: no separate pass over dO and O
+  // for bwd_dkdv, which runs behind this kernel on the same stream: no separate pass over dO and O.
+  // It is summed on the matrix core exactly as dP is -- D = O dO^T with the O rows where the tile loop has the V rows, delta = its
+  // diagonal -- so that dP - delta cancels the way it does in exact arithmetic where one key holds (nearly) the whole row, O = V[key]:
+  // a plain dot product rounds differently from dP and leaves |dP| eps in a dS that should be 0 (dQ, dK of a single key: 1e-6 in
+  // place of 0).  16 MFMAs per wave, once.
   const float *op = a.o + b * a.so.b + hd * a.so.h + (long long)qc * a.so.t + 16 * h;
   float qreg[16], doreg[16];
-  float delta = 0.f;
+  f32x16 dd = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const float4 t = ld4(qp + 4 * i), u = ld4(dop + 4 * i), w = ld4(op + 4 * i);
     qreg[4 * i] = t.x * a.scale_log2; qreg[4 * i + 1] = t.y * a.scale_log2;
     qreg[4 * i + 2] = t.z * a.scale_log2; qreg[4 * i + 3] = t.w * a.scale_log2;
     doreg[4 * i] = u.x; doreg[4 * i + 1] = u.y; doreg[4 * i + 2] = u.z; doreg[4 * i + 3] = u.w;
-    delta += u.x * w.x + u.y * w.y + u.z * w.z + u.w * w.w;
+    dd = mfma(w.x, u.x, dd); dd = mfma(w.y, u.y, dd); dd = mfma(w.z, u.z, dd); dd = mfma(w.w, u.w, dd);
   }
-  delta += xhalf(delta);
+  // D[i][r] of the wave's queries i lies in register v of lane half h with i = (v & 3) + 8 (v >> 2) + 4 h: the diagonal element of
+  // query r in half (r >> 2) & 1, register (r & 3) + 4 (r >> 3)
+  const int vsel = (r & 3) + 4 * (r >> 3);
+  float dsel = dd[0];
+#pragma unroll
+  for (int v = 1; v < 16; ++v) dsel = (vsel == v) ? dd[v] : dsel;
+  const float dother = xhalf(dsel);
+  const float delta = (h == ((r >> 2) & 1)) ? dsel : dother;
   if (h == 0 && q < a.Lq) const_cast<float *>(a.delta)[(long long)bh * a.Lq + q] = delta;
   const float lse = a.lse[(long long)bh * a.Lq + qc];
   const float *kb = a.k + b * a.sk.b + hd * a.sk.h, *vb = a.v + b * a.sv.b + hd * a.sv.h;
@@ -464,8 +475,7 @@ __global__ __launch_bounds__(256, ATTN_BWD_WAVES) void bwd_dkdv_kernel(const Arg
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const float4 t = ld4(kp + 4 * i), u = ld4(vp + 4 * i);
-    kreg[4 * i] = t.x * a.scale_log2; kreg[4 * i + 1] = t.y * a.scale_log2;
-    kreg[4 * i + 2] = t.z * a.scale_log2; kreg[4 * i + 3] = t.w * a.scale_log2;
+    kreg[4 * i] = t.x; kreg[4 * i + 1] = t.y; kreg[4 * i + 2] = t.z; kreg[4 * i + 3] = t.w;
     vreg[4 * i] = u.x; vreg[4 * i + 1] = u.y; vreg[4 * i + 2] = u.z; vreg[4 * i + 3] = u.w;
   }
   // MASK: this lane's key takes no part in any softmax -- P = 0 in its whole column, dK = dV = 0
@@ -506,7 +516,11 @@ __global__ __launch_bounds__(256, ATTN_BWD_WAVES) void bwd_dkdv_kernel(const Arg
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int idx = threadIdx.x + 256 * j, row = idx >> 3, c = (idx & 7) * 4;
-      *reinterpret_cast<float4 *>(&Qs[buf][row * kKStride + c]) = qr[j];
+      // Q goes into LDS pre-scaled exactly as the forward pre-scales it: S = (Q scale_log2) K^T is then built from the products the
+      // forward's lse normalises.  (With the scale on K instead, each score rounds differently from the forward's and exp2(s - lse)
+      // loses the row's normalisation: 3 - 4 x the float32 error in dK / dV on peaked rows with logits of 50 - 80.)
+      *reinterpret_cast<float4 *>(&Qs[buf][row * kKStride + c]) =
+          make_float4(qr[j].x * a.scale_log2, qr[j].y * a.scale_log2, qr[j].z * a.scale_log2, qr[j].w * a.scale_log2);
       *reinterpret_cast<float4 *>(&Ds[buf][row * kKStride + c]) = dr[j];
     }
     if (threadIdx.x < kTileK) { Ls[buf][threadIdx.x] = lr; Es[buf][threadIdx.x] = er; }
@@ -565,7 +579,8 @@ __global__ __launch_bounds__(256, ATTN_BWD_WAVES) void bwd_dkdv_kernel(const Arg
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int v = 4 * g + j;
-          const float p = dead ? 0.f : ((ATTN_SKIP & 1) ? s[v] - ls[j] : __builtin_amdgcn_exp2f(s[v] - ls[j]));
+          const float sv = dead ? -INFINITY : s[v];             // exp2(-inf - lse) = 0; NaN where the whole row is padded (lse = -inf), like o
+          const float p = (ATTN_SKIP & 1) ? sv - ls[j] : __builtin_amdgcn_exp2f(sv - ls[j]);
           float pd = p, dpe = dp[v];
           if (DROP && !(ATTN_SKIP & 2)) {
             bool keep;
@@ -628,11 +643,13 @@ __global__ __launch_bounds__(256, ATTN_BWD_WAVES) void bwd_dkdv_kernel(const Arg
   const int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   const int key_e = (int)blockIdx.x * kBlockQ + wave_s * 32 + (lane_e & 31), h_e = lane_e >> 5;
   if (key_e < a.Lk) {
+    // dK = scale dS^T Q from the accumulated dS^T (Q scale_log2): scale / scale_log2 = ln 2
+    constexpr float kLn2 = 0.6931471805599453f;
     float *dkp = a.dk + b * a.sdk.b + hd * a.sdk.h + (long long)key_e * a.sdk.t + 4 * h_e;
     float *dvp = a.dv + b * a.sdv.b + hd * a.sdv.h + (long long)key_e * a.sdv.t + 4 * h_e;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      *reinterpret_cast<float4 *>(dkp + 8 * g) = make_float4(dk[4 * g] * a.scale, dk[4 * g + 1] * a.scale, dk[4 * g + 2] * a.scale, dk[4 * g + 3] * a.scale);
+      *reinterpret_cast<float4 *>(dkp + 8 * g) = make_float4(dk[4 * g] * kLn2, dk[4 * g + 1] * kLn2, dk[4 * g + 2] * kLn2, dk[4 * g + 3] * kLn2);
       *reinterpret_cast<float4 *>(dvp + 8 * g) = make_float4(dv[4 * g], dv[4 * g + 1], dv[4 * g + 2], dv[4 * g + 3]);
     }
   }
