@@ -107,6 +107,25 @@ int mono_matched_losses_bwd_f32(const float *boxes, const float *depth, const fl
  * (int32 elements per chunk, any size), then wd[n_chunks] (float weight decay). */
 int mono_adamw_step_f32(const void *table, int n_chunks, double beta1, double beta2, double eps, double step_size, void *stream);
 
+/* The guard in front of that step: gradient-norm clipping and the skipping of a step with non-finite gradients, decided on the device.
+ * The guard record (device memory, 24 bytes, 8-byte aligned, zeroed once by the caller):
+ *     float     norm            global L2 norm of all gradients of the step: (float)sqrt(sum of (double)g * (double)g)
+ *     float     coef            fminf(max_norm / (norm + 1e-6f), 1.0f) in f32 (torch.nn.utils.clip_grad_norm_), 1.0f without clipping
+ *     int       skip            1 when skip_nonfinite is set and the sum of squares is NaN or Inf, else 0
+ *     int       (padding)
+ *     long long skipped_total   number of calls that set skip, since the record was zeroed
+ * mono_grad_guard_f32: tables / n_chunks are HOST arrays of n_groups (1..8) device chunk tables of the layout above and their chunk
+ * counts; the g and n columns of all of them are read, so the norm is global.  partials: device scratch of sum(n_chunks) doubles.
+ * max_norm <= 0: no clipping.  Two launches: one workgroup per chunk writes one f64 partial (exact products, so neither 1e25- nor
+ * 1e-30-sized gradients overflow or vanish), one workgroup adds them in chunk order; no atomics, bit-reproducible.
+ * mono_adamw_step_guarded_f32: mono_adamw_step_f32 under a record written earlier on the same stream.  skip != 0: nothing is stored
+ * (p, m, v keep their bits).  Otherwise every gradient element is used as g * coef (one f32 rounding), so the result is bit for bit
+ * that of mono_adamw_step_f32 on gradients multiplied by coef beforehand.  The gradients themselves are never rewritten. */
+int mono_grad_guard_f32(const void *const *tables, const int *n_chunks, int n_groups, float max_norm, int skip_nonfinite,
+                        double *partials, void *record, void *stream);
+int mono_adamw_step_guarded_f32(const void *table, int n_chunks, double beta1, double beta2, double eps, double step_size,
+                                const void *record, void *stream);
+
 /* dW[M, N] = dY[R, M]^T . X[R, N] and (db != NULL) db[M] = the column sums of dY, f32, exact products (v_mfma_f32_32x32x2_f32), summed in a
  * fixed order (no atomics): the weight and bias gradients of y = x W^T + b over a few thousand tokens -- autograd's AddmmBackward of the
  * nn.Linear layers of the decoder / depth-token encoder (reference depthaware_transformer.py:339-354,440-515) -- in two launches that

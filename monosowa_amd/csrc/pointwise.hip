@@ -563,11 +563,30 @@ __device__ __forceinline__ void adamw_one(float &p, float g, float &m, float &v,
   p = __fmaf_rn(neg_step, upd, p);
 }
 
+// The guard record (include/monosowa_pointwise.h): written by grad_guard_fold_kernel, read by adamw_kernel.
+struct GuardRecord {
+  float norm;                 // global L2 norm of every gradient of the step
+  float coef;                 // clip_grad_norm_'s factor, 1 when clipping is off
+  int skip;                   // 1: the gradients of this step are not finite and the update is to be left out
+  int pad;
+  long long skipped_total;    // steps left out since the record was zeroed
+};
+
+// rec == nullptr: the plain step.  Otherwise the step under the guard: nothing is stored when rec->skip is set, and every
+// gradient element enters adamw_one as g * rec->coef (one rounding, like a torch multiply in front of the plain step).
 __global__ __launch_bounds__(256) void adamw_kernel(const unsigned long long *__restrict__ pp, const unsigned long long *__restrict__ gp,
                                                     const unsigned long long *__restrict__ mp, const unsigned long long *__restrict__ vp,
                                                     const int *__restrict__ ns, const float *__restrict__ wds, float b1, float omb1,
-                                                    float b2, float omb2, float eps, float step_size) {
+                                                    float b2, float omb2, float eps, float step_size,
+                                                    const GuardRecord *__restrict__ rec) {
   const int c = blockIdx.x;
+  const bool guarded = rec != nullptr;
+  float coef = 1.f;
+  if (guarded) {
+    if (rec->skip) return;
+    coef = rec->coef;
+  }
+  auto scaled = [guarded, coef](float x) { return guarded ? __fmul_rn(x, coef) : x; };
   float *p = reinterpret_cast<float *>(pp[c]), *m = reinterpret_cast<float *>(mp[c]), *v = reinterpret_cast<float *>(vp[c]);
   const float *g = reinterpret_cast<const float *>(gp[c]);
   const int n = ns[c];
@@ -577,15 +596,83 @@ __global__ __launch_bounds__(256) void adamw_kernel(const unsigned long long *__
     for (int i = threadIdx.x; i < n4; i += 256) {
       float4 P = reinterpret_cast<float4 *>(p)[i], M = reinterpret_cast<float4 *>(m)[i], V = reinterpret_cast<float4 *>(v)[i];
       const float4 G = reinterpret_cast<const float4 *>(g)[i];
-      adamw_one(P.x, G.x, M.x, V.x, wd, b1, omb1, b2, omb2, eps, neg);
-      adamw_one(P.y, G.y, M.y, V.y, wd, b1, omb1, b2, omb2, eps, neg);
-      adamw_one(P.z, G.z, M.z, V.z, wd, b1, omb1, b2, omb2, eps, neg);
-      adamw_one(P.w, G.w, M.w, V.w, wd, b1, omb1, b2, omb2, eps, neg);
+      adamw_one(P.x, scaled(G.x), M.x, V.x, wd, b1, omb1, b2, omb2, eps, neg);
+      adamw_one(P.y, scaled(G.y), M.y, V.y, wd, b1, omb1, b2, omb2, eps, neg);
+      adamw_one(P.z, scaled(G.z), M.z, V.z, wd, b1, omb1, b2, omb2, eps, neg);
+      adamw_one(P.w, scaled(G.w), M.w, V.w, wd, b1, omb1, b2, omb2, eps, neg);
       reinterpret_cast<float4 *>(p)[i] = P; reinterpret_cast<float4 *>(m)[i] = M; reinterpret_cast<float4 *>(v)[i] = V;
     }
-    for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) adamw_one(p[i], g[i], m[i], v[i], wd, b1, omb1, b2, omb2, eps, neg);
+    for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) adamw_one(p[i], scaled(g[i]), m[i], v[i], wd, b1, omb1, b2, omb2, eps, neg);
   } else {
-    for (int i = threadIdx.x; i < n; i += 256) adamw_one(p[i], g[i], m[i], v[i], wd, b1, omb1, b2, omb2, eps, neg);
+    for (int i = threadIdx.x; i < n; i += 256) adamw_one(p[i], scaled(g[i]), m[i], v[i], wd, b1, omb1, b2, omb2, eps, neg);
+  }
+}
+
+// ---- the guard in front of the AdamW step: global gradient norm, clip factor, non-finite record --------------------------
+// Chunk tables of up to GUARD_MAX_GROUPS parameter groups (the g and n columns of the tables adamw_kernel reads); first[k] = number
+// of chunks in the groups before k, first[count] = all of them.
+constexpr int GUARD_MAX_GROUPS = 8;
+struct GuardGroups {
+  const unsigned long long *g[GUARD_MAX_GROUPS];
+  const int *n[GUARD_MAX_GROUPS];
+  int first[GUARD_MAX_GROUPS + 1];
+  int count;
+};
+
+// The 256 per-thread sums of a workgroup in a fixed order: xor butterfly inside each wave, then the four wave sums in wave order.
+__device__ __forceinline__ double guard_block_sum(double acc, double *red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// One workgroup per chunk: partials[chunk] = sum of (double)g * (double)g.  The products are exact in f64 (24-bit factors), so
+// neither 1e25-sized nor 1e-30-sized gradients overflow or vanish; NaN and +-Inf come out as NaN / +Inf of the sum.
+__global__ __launch_bounds__(256) void grad_guard_partial_kernel(GuardGroups t, double *__restrict__ partials) {
+  const int c = blockIdx.x;
+  const unsigned long long *gcol = t.g[0];
+  const int *ncol = t.n[0];
+  int base = 0;
+#pragma unroll
+  for (int k = 1; k < GUARD_MAX_GROUPS; ++k)
+    if (k < t.count && c >= t.first[k]) { gcol = t.g[k]; ncol = t.n[k]; base = t.first[k]; }
+  const unsigned long long addr = gcol[c - base];
+  const float *g = reinterpret_cast<const float *>(addr);
+  const int n = ncol[c - base];
+  double acc = 0.0;
+  auto add = [&acc](float x) { const double d = (double)x; acc = fma(d, d, acc); };
+  if ((addr & 15ull) == 0) {
+    const int n4 = n >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      const float4 G = reinterpret_cast<const float4 *>(g)[i];
+      add(G.x); add(G.y); add(G.z); add(G.w);
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) add(g[i]);
+  } else {
+    for (int i = threadIdx.x; i < n; i += 256) add(g[i]);
+  }
+  __shared__ double red[4];
+  const double s = guard_block_sum(acc, red);
+  if (threadIdx.x == 0) partials[c] = s;
+}
+
+// One workgroup: thread t adds partials t, t + 256, ... in chunk order, the 256 sums are added in a fixed order, thread 0 writes
+// the record.
+__global__ __launch_bounds__(256) void grad_guard_fold_kernel(const double *__restrict__ partials, int n_chunks, float max_norm,
+                                                              int skip_nonfinite, GuardRecord *__restrict__ rec) {
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n_chunks; i += 256) acc += partials[i];
+  __shared__ double red[4];
+  const double sumsq = guard_block_sum(acc, red);
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(sumsq);
+    const int skip = (skip_nonfinite && !isfinite(sumsq)) ? 1 : 0;
+    rec->norm = norm;
+    rec->coef = max_norm > 0.f ? fminf(__fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f)), 1.0f) : 1.0f;
+    rec->skip = skip;
+    rec->skipped_total = rec->skipped_total + skip;
   }
 }
 
@@ -852,7 +939,8 @@ int mono_matched_losses_bwd_f32(const float *boxes, const float *depth, const fl
 // back, p[n_chunks], g[n_chunks], m[n_chunks], v[n_chunks] (64-bit device addresses), n[n_chunks] (int32, elements
 // per chunk), wd[n_chunks] (float).  step_size = lr * sqrt(1 - b2^t) / (1 - b1^t).  Scalars arrive as doubles so that
 // 1 - beta is rounded to float once, like the Python scalars of the reference.
-int mono_adamw_step_f32(const void *table, int n_chunks, double beta1, double beta2, double eps, double step_size, void *stream_) {
+static int adamw_launch(const void *table, int n_chunks, double beta1, double beta2, double eps, double step_size, const void *record,
+                        void *stream_) {
   if (!table) return -1;
   if (n_chunks <= 0) return -2;
   const unsigned long long *pp = reinterpret_cast<const unsigned long long *>(table);
@@ -860,7 +948,50 @@ int mono_adamw_step_f32(const void *table, int n_chunks, double beta1, double be
   const float *wds = reinterpret_cast<const float *>(ns + n_chunks);
   mono::adamw_kernel<<<n_chunks, 256, 0, (hipStream_t)stream_>>>(pp, pp + n_chunks, pp + 2 * (size_t)n_chunks, pp + 3 * (size_t)n_chunks,
                                                                ns, wds, (float)beta1, (float)(1.0 - beta1), (float)beta2,
-                                                               (float)(1.0 - beta2), (float)eps, (float)step_size);
+                                                               (float)(1.0 - beta2), (float)eps, (float)step_size,
+                                                               reinterpret_cast<const mono::GuardRecord *>(record));
+  return (int)hipGetLastError();
+}
+
+int mono_adamw_step_f32(const void *table, int n_chunks, double beta1, double beta2, double eps, double step_size, void *stream_) {
+  return adamw_launch(table, n_chunks, beta1, beta2, eps, step_size, nullptr, stream_);
+}
+
+// The same step under the guard record mono_grad_guard_f32 wrote on this stream: no store at all when record->skip is set, every
+// gradient element taken times record->coef otherwise (the gradients themselves are not rewritten).
+int mono_adamw_step_guarded_f32(const void *table, int n_chunks, double beta1, double beta2, double eps, double step_size,
+                                const void *record, void *stream_) {
+  if (!record) return -1;
+  return adamw_launch(table, n_chunks, beta1, beta2, eps, step_size, record, stream_);
+}
+
+// Global L2 norm of the gradients of n_groups chunk tables (the layout of mono_adamw_step_f32; the g and n columns are read) and the
+// guard record, in two launches, fixed summation order, no atomics: the same inputs give the same record bit for bit.
+// tables / n_chunks: HOST arrays of n_groups device tables and their chunk counts (1 <= n_groups <= 8).  partials: device scratch of
+// sum(n_chunks) doubles.  record: the 24-byte device record of include/monosowa_pointwise.h, zeroed once by the caller;
+// skipped_total accumulates over the calls.  max_norm <= 0: no clipping (coef = 1).
+int mono_grad_guard_f32(const void *const *tables, const int *n_chunks, int n_groups, float max_norm, int skip_nonfinite,
+                        double *partials, void *record, void *stream_) {
+  if (!tables || !n_chunks || !partials || !record) return -1;
+  if (n_groups <= 0 || n_groups > mono::GUARD_MAX_GROUPS) return -2;
+  mono::GuardGroups t = {};
+  long long total = 0;
+  for (int k = 0; k < n_groups; ++k) {
+    if (!tables[k]) return -1;
+    if (n_chunks[k] <= 0) return -2;
+    const unsigned long long *pp = reinterpret_cast<const unsigned long long *>(tables[k]);
+    t.g[k] = pp + n_chunks[k];
+    t.n[k] = reinterpret_cast<const int *>(pp + 4 * (size_t)n_chunks[k]);
+    t.first[k] = (int)total;
+    total += n_chunks[k];
+    if (total > 0x7fffffffLL) return -2;
+  }
+  for (int k = n_groups; k <= mono::GUARD_MAX_GROUPS; ++k) t.first[k] = (int)total;
+  t.count = n_groups;
+  hipStream_t st = (hipStream_t)stream_;
+  mono::grad_guard_partial_kernel<<<(int)total, 256, 0, st>>>(t, partials);
+  mono::grad_guard_fold_kernel<<<1, 256, 0, st>>>(partials, (int)total, max_norm, skip_nonfinite,
+                                                 reinterpret_cast<mono::GuardRecord *>(record));
   return (int)hipGetLastError();
 }
 

@@ -6,6 +6,9 @@ checkpoint naming.  Differences that do not change results:
   (bucketed RCCL all-reduce overlapped with backward); rank 0 alone writes checkpoints and logs.
 * the per-iteration ``.item()`` of ~30 loss terms (a host sync every step, :153-157) happens only on
   the logging iterations (every 30th, as printed by the reference).
+* with ``optimizer.clip_max_norm`` / ``optimizer.skip_nonfinite`` configured (optimizer_helper.py) the logging iterations
+  also print the gradient norm and the number of skipped steps, and an epoch in which EVERY step was skipped raises
+  instead of writing a checkpoint; without the keys the printed lines are the reference's.
 """
 import os
 
@@ -95,6 +98,7 @@ class Trainer(object):
         self.output_dir = os.path.join("./" + cfg["save_path"], model_name)
         self.tester = None
         self.log_interval = 30
+        self._guard_skipped = 0          # optimizer.guard_report()["skipped_total"] at the end of the previous epoch
 
         if cfg.get("pretrain_model"):
             assert os.path.exists(cfg["pretrain_model"])
@@ -170,9 +174,11 @@ class Trainer(object):
         if main:
             print(">>>>>>> Epoch:", str(epoch) + ":")
         bar = tqdm.tqdm(total=len(self.train_loader), leave=(self.epoch + 1 == self.cfg["max_epoch"]), desc="iters", disable=not main)
+        steps = 0
         for batch_idx, raw in enumerate(self.train_loader):
             inputs, calibs, targets, info = stage_batch(raw, self.device)
             total, loss_dict = self.train_step(inputs, calibs, targets, info)
+            steps += 1
             if batch_idx % self.log_interval == 0:
                 self._log(batch_idx, loss_dict)
             bar.update()
@@ -182,6 +188,25 @@ class Trainer(object):
         matcher = getattr(self.detr_loss, "matcher", None)
         if matcher is not None and hasattr(matcher, "check_device_status"):
             matcher.check_device_status(block=True)
+        self._check_guard(epoch, steps)
+
+    def _guard_report(self):
+        """The optimizer's guard record when the guarded step is configured (a host synchronisation), else None."""
+        if not getattr(self.optimizer, "guard_enabled", False):
+            return None
+        return self.optimizer.guard_report()
+
+    def _check_guard(self, epoch, steps):
+        """End of an epoch under the guarded step: how many of its steps were skipped for non-finite gradients; all of them means
+        the model is not training, and the epoch's checkpoint must not look healthy."""
+        report = self._guard_report()
+        if report is None:
+            return
+        skipped = report["skipped_total"] - self._guard_skipped
+        self._guard_skipped = report["skipped_total"]
+        self.logger.info("Epoch {}: {} of {} steps skipped (non-finite gradients)".format(epoch, skipped, steps))
+        if steps > 0 and skipped >= steps:
+            raise RuntimeError("every step of epoch %d (%d) was skipped for non-finite gradients: the model is not training" % (epoch, steps))
 
     def _log(self, batch_idx, loss_dict):
         weight_dict = self.detr_loss.weight_dict
@@ -198,6 +223,9 @@ class Trainer(object):
                 seen.add(key[-1])
             print("%s: %.2f, " % (key, val), end="")
         print("\n")
+        report = self._guard_report()
+        if report is not None:
+            print("grad_norm: %.4g, skipped: %d\n" % (report["grad_norm"], report["skipped_total"]))
 
     @staticmethod
     def prepare_targets(targets, batch_size):

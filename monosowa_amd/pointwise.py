@@ -11,7 +11,7 @@ from ._lib import raw_stream, on_device, DeterministicSwitch, alert_not_determin
 
 _PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmonosowa_pointwise.so")
 SYMBOLS = ("mono_bias_act_f32", "mono_bias_relu_maxpool_nhwc_f32", "mono_conv1x1_tail_f32", "mono_conv1x1_tail_ds_f32", "mono_conv1x1_head_f32", "mono_relu_grad_f32", "mono_relu_grad2_f32", "mono_relu_grad3_f32", "mono_bias_relu_mask_f32", "mono_relu_grad_mask_f32", "mono_affine_relu_mask_f32", "mono_affine_relu_grad_f32", "mono_dropout_add_layernorm_fwd_f32",
-           "mono_dropout_add_layernorm_bwd_f32", "mono_groupnorm_nhwc_fwd_f32", "mono_groupnorm_nhwc_bwd_f32", "mono_groupnorm_blocks", "mono_colsum_f32", "mono_colsum_strided_f32", "mono_reduce_blocks", "mono_adamw_step_f32", "mono_relu_dropout_fwd_f32",
+           "mono_dropout_add_layernorm_bwd_f32", "mono_groupnorm_nhwc_fwd_f32", "mono_groupnorm_nhwc_bwd_f32", "mono_groupnorm_blocks", "mono_colsum_f32", "mono_colsum_strided_f32", "mono_reduce_blocks", "mono_adamw_step_f32", "mono_adamw_step_guarded_f32", "mono_grad_guard_f32", "mono_relu_dropout_fwd_f32",
            "mono_relu_dropout_bwd_f32", "mono_matched_losses_fwd_f32", "mono_matched_losses_bwd_f32", "mono_ddn_loss_blocks",
            "mono_ddn_loss_fwd_f32", "mono_ddn_loss_bwd_f32", "mono_depth_expect_fwd_f32", "mono_depth_expect_bwd_f32", "mono_focal_fwd_f32", "mono_focal_bwd_f32", "mono_head_tail_fwd_f32", "mono_head_tail_bwd_f32", "mono_match_cost_f32", "mono_refine_reference_f32", "mono_relu_dropout_bwd_colsum_f32", "mono_sum_slices_f32", "mono_colsum_any_blocks", "mono_colsum_any_f32", "mono_relu_grad_mask3_f32", "mono_lsap_match_flat_f32",
            "mono_linear_wgrad_workspace", "mono_linear_wgrad_f32", "mono_colsum_levels_blocks", "mono_colsum_levels_f32", "mono_relu_grad_scale_f32",
@@ -92,6 +92,10 @@ def load():
         lib.mono_matched_losses_bwd_f32.argtypes = [P] * 16 + [I] * 4 + [P]
         lib.mono_adamw_step_f32.restype = I
         lib.mono_adamw_step_f32.argtypes = [P, I] + [ctypes.c_double] * 4 + [P]
+        lib.mono_adamw_step_guarded_f32.restype = I
+        lib.mono_adamw_step_guarded_f32.argtypes = [P, I] + [ctypes.c_double] * 4 + [P, P]
+        lib.mono_grad_guard_f32.restype = I
+        lib.mono_grad_guard_f32.argtypes = [P, P, I, ctypes.c_float, I, P, P, P]
         lib.mono_colsum_strided_f32.restype = I
         lib.mono_colsum_strided_f32.argtypes = [P, P, P, I, LL, LL, I, P]
         lib.mono_colsum_levels_blocks.restype = I
@@ -788,7 +792,8 @@ class FusedAdamWPlan:
         ptr = lambda ts: self.np.array([t.data_ptr() for t in ts], dtype=self.np.uint64)
         return all(self.np.array_equal(a, ptr(b)) for a, b in zip(self.keys, (params, exp_avgs, exp_avg_sqs)))
 
-    def step(self, grads, beta1, beta2, eps, step_size):
+    def refresh(self, grads):
+        """This step's gradient addresses into the table, and the table on its way to the device."""
         np = self.np
         g = np.array([t.data_ptr() for t in grads], dtype=np.uint64)
         if getattr(self, "copied", None) is not None:
@@ -797,11 +802,59 @@ class FusedAdamWPlan:
         self.dev.copy_(self.host, non_blocking=True)
         self.copied = torch.cuda.Event()
         self.copied.record()
+
+    def launch(self, beta1, beta2, eps, step_size, record=None):
+        """The update from the refreshed table; ``record``: device address of a guard record (``GradGuard``) the kernel consults."""
         with on_device(self.device):
-            code = load().mono_adamw_step_f32(self.dev.data_ptr(), self.n_chunks, beta1, beta2, eps, step_size,
-                                              raw_stream())
+            if record is None:
+                name = "mono_adamw_step_f32"
+                code = load().mono_adamw_step_f32(self.dev.data_ptr(), self.n_chunks, beta1, beta2, eps, step_size, raw_stream())
+            else:
+                name = "mono_adamw_step_guarded_f32"
+                code = load().mono_adamw_step_guarded_f32(self.dev.data_ptr(), self.n_chunks, beta1, beta2, eps, step_size, record,
+                                                          raw_stream())
         if code:
-            raise RuntimeError("mono_adamw_step_f32 failed with code %d" % code)
+            raise RuntimeError("%s failed with code %d" % (name, code))
+
+    def step(self, grads, beta1, beta2, eps, step_size):
+        self.refresh(grads)
+        self.launch(beta1, beta2, eps, step_size)
+
+
+GUARD_MAX_GROUPS = 8          # chunk tables one mono_grad_guard_f32 call takes
+GUARD_RECORD_BYTES = 24       # float norm, float coef, int skip, int padding, long long skipped_total
+
+
+class GradGuard:
+    """Device-side guard in front of the fused AdamW step (``mono_grad_guard_f32``): the global L2 norm of the gradients of all
+    refreshed ``FusedAdamWPlan`` tables, the clip factor and the non-finite record, in two launches and without a host
+    synchronisation.  The record lives as long as the guard: ``skipped_total`` counts over the steps."""
+
+    def __init__(self, device):
+        self.device = device
+        self.record = torch.zeros(GUARD_RECORD_BYTES // 8, dtype=torch.int64, device=device)      # 8-byte aligned, zeroed once
+        self.partials = None
+
+    def run(self, plans, max_norm, skip_nonfinite):
+        """Writes the record for the gradients the ``plans`` (refreshed on the current stream) point at."""
+        if not 1 <= len(plans) <= GUARD_MAX_GROUPS:
+            raise ValueError("GradGuard.run takes 1 to %d chunk tables, not %d" % (GUARD_MAX_GROUPS, len(plans)))
+        total = sum(p.n_chunks for p in plans)
+        if self.partials is None or self.partials.numel() < total:
+            self.partials = torch.empty(total, dtype=torch.float64, device=self.device)
+        tables = (ctypes.c_void_p * len(plans))(*[p.dev.data_ptr() for p in plans])
+        counts = (ctypes.c_int * len(plans))(*[p.n_chunks for p in plans])
+        with on_device(self.device):
+            code = load().mono_grad_guard_f32(tables, counts, len(plans), float(max_norm or 0.0), int(bool(skip_nonfinite)),
+                                              self.partials.data_ptr(), self.record.data_ptr(), raw_stream())
+        if code:
+            raise RuntimeError("mono_grad_guard_f32 failed with code %d" % code)
+
+    def report(self):
+        """The record as ``{"grad_norm", "coef", "skip", "skipped_total"}``; waits for the device."""
+        raw = self.record.cpu().numpy().view(np.uint8)
+        return {"grad_norm": float(raw[0:4].view(np.float32)[0]), "coef": float(raw[4:8].view(np.float32)[0]),
+                "skip": int(raw[8:12].view(np.int32)[0]), "skipped_total": int(raw[16:24].view(np.int64)[0])}
 
 
 # ---------------------------------------------------------------------------------------------------------
