@@ -40,7 +40,7 @@ int mono_conv1x1_head_f32(const float *x, const float *w, const float *b_out, fl
 
 /* grad_in[i] = y[i] > 0 ? grad_out[i] : 0   (n % 4 == 0; grad_in may alias grad_out). */
 int mono_relu_grad_f32(const float *grad_out, const float *y, float *grad_in, long long n, void *stream);
-/* grad_in = scale[c] * grad_out * (y > 0) on a channels-last tensor of n elements, C channels (C % 4 == 0, n % C == 0): the same with the
+/* grad_in = scale[c] * grad_out * (y > 0 or NaN) on a channels-last tensor of n elements, C channels (C % 4 == 0, n % C == 0): the same with the
  * frozen norm's scale put on the gradient (trainable 1 x 1 convolution + frozen BN + ReLU without an identity branch, backbone.py:72-115). */
 int mono_relu_grad_scale_f32(const float *grad_out, const float *y, const float *scale, float *grad_in, long long n, int C, void *stream);
 
@@ -61,7 +61,7 @@ int mono_affine_relu_mask_f32(float *y, const float *scale, const float *shift, 
 int mono_affine_relu_grad_f32(const float *grad, const unsigned char *mask, const float *scale, float *grad_in, long long rows,
                               int C, void *stream);
 
-/* grad_in = (grad_a + grad_b) * (y > 0): ReLU backward of a tensor with two consumers (ResNet block output -> next
+/* grad_in = (grad_a + grad_b) * (y > 0 or NaN): ReLU backward of a tensor with two consumers (ResNet block output -> next
  * convolution and identity branch, backbone.py:64-82 of the reference's torchvision ResNet) in one pass. */
 int mono_relu_grad2_f32(const float *grad_a, const float *grad_b, const float *y, float *grad_in, long long n, void *stream);
 /* the same for three consumers: grad_in[i] = y[i] > 0 ? (grad_a[i] + grad_b[i]) + grad_c[i] : 0 */
@@ -78,7 +78,7 @@ int mono_dropout_add_layernorm_fwd_f32(const float *x, const float *z, const flo
 /* y = dropout_p(relu(h)) over n contiguous floats (n % 4 == 0), hash mask from (seed, element index); the FFN hidden
  * activation `self.dropout2(F.relu(self.linear1(src)))` (depthaware_transformer.py:352,513, transformer.py:63). */
 int mono_relu_dropout_fwd_f32(const float *h, float *y, long long n, float p, unsigned long long seed, void *stream);
-/* grad_h = grad_y / (1 - p) where y > 0 (kept and h > 0), else 0. */
+/* grad_h = grad_y / (1 - p) where y > 0 (kept and h > 0) or y is NaN, else 0. */
 int mono_relu_dropout_bwd_f32(const float *grad_y, const float *y, float *grad_h, long long n, float p, void *stream);
 /* The same over a [rows, 256] matrix, plus colsum[256] = column sums of grad_h (the bias gradient of the linear in front);
  * partials: mono_reduce_blocks(rows) * 256 floats of scratch. */

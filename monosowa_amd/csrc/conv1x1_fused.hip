@@ -17,6 +17,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "relu_nan.h"
+
 namespace mono {
 
 typedef float c1_f32x16 __attribute__((ext_vector_type(16)));
@@ -44,8 +46,8 @@ __global__ __launch_bounds__(kC1Threads) void conv1x1_tail_kernel(const float *_
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const float4 v = *reinterpret_cast<const float4 *>(xp + 4 * i), b = *reinterpret_cast<const float4 *>(&Bi[32 * kh + 4 * i]);
-      xr[4 * i] = fmaxf(v.x + b.x, 0.f); xr[4 * i + 1] = fmaxf(v.y + b.y, 0.f);
-      xr[4 * i + 2] = fmaxf(v.z + b.z, 0.f); xr[4 * i + 3] = fmaxf(v.w + b.w, 0.f);
+      xr[4 * i] = relu_f(v.x + b.x); xr[4 * i + 1] = relu_f(v.y + b.y);
+      xr[4 * i + 2] = relu_f(v.z + b.z); xr[4 * i + 3] = relu_f(v.w + b.w);
     }
     const float *rp = res + mc * kC1N + 4 * kh;
     float *yp = y + mc * kC1N + 4 * kh;
@@ -71,8 +73,8 @@ __global__ __launch_bounds__(kC1Threads) void conv1x1_tail_kernel(const float *_
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const float4 bo = *reinterpret_cast<const float4 *>(&Bo[nb * 32 + 8 * g + 4 * kh]);
-        const float4 o = make_float4(fmaxf(acc[4 * g] + bo.x + r4[g].x, 0.f), fmaxf(acc[4 * g + 1] + bo.y + r4[g].y, 0.f),
-                                     fmaxf(acc[4 * g + 2] + bo.z + r4[g].z, 0.f), fmaxf(acc[4 * g + 3] + bo.w + r4[g].w, 0.f));
+        const float4 o = make_float4(relu_f(acc[4 * g] + bo.x + r4[g].x), relu_f(acc[4 * g + 1] + bo.y + r4[g].y),
+                                     relu_f(acc[4 * g + 2] + bo.z + r4[g].z), relu_f(acc[4 * g + 3] + bo.w + r4[g].w));
         if (live) *reinterpret_cast<float4 *>(yp + nb * 32 + 8 * g) = o;
       }
     }
@@ -109,8 +111,8 @@ __global__ __launch_bounds__(kC1Threads2) void conv1x1_tail_ds_kernel(const floa
     for (int i = 0; i < 8; ++i) {
       const float4 v = *reinterpret_cast<const float4 *>(xp + 4 * i), b = *reinterpret_cast<const float4 *>(&Bi[32 * kh + 4 * i]);
       const float4 u = *reinterpret_cast<const float4 *>(x0p + 4 * i);
-      xr[4 * i] = fmaxf(v.x + b.x, 0.f); xr[4 * i + 1] = fmaxf(v.y + b.y, 0.f);
-      xr[4 * i + 2] = fmaxf(v.z + b.z, 0.f); xr[4 * i + 3] = fmaxf(v.w + b.w, 0.f);
+      xr[4 * i] = relu_f(v.x + b.x); xr[4 * i + 1] = relu_f(v.y + b.y);
+      xr[4 * i + 2] = relu_f(v.z + b.z); xr[4 * i + 3] = relu_f(v.w + b.w);
       x0r[4 * i] = u.x; x0r[4 * i + 1] = u.y; x0r[4 * i + 2] = u.z; x0r[4 * i + 3] = u.w;
     }
     float *yp = y + mc * kC1N + 4 * kh;
@@ -125,8 +127,8 @@ __global__ __launch_bounds__(kC1Threads2) void conv1x1_tail_ds_kernel(const floa
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const float4 bo = *reinterpret_cast<const float4 *>(&Bo[nb * 32 + 8 * g + 4 * kh]);
-        const float4 o = make_float4(fmaxf(acc[4 * g] + bo.x, 0.f), fmaxf(acc[4 * g + 1] + bo.y, 0.f),
-                                     fmaxf(acc[4 * g + 2] + bo.z, 0.f), fmaxf(acc[4 * g + 3] + bo.w, 0.f));
+        const float4 o = make_float4(relu_f(acc[4 * g] + bo.x), relu_f(acc[4 * g + 1] + bo.y),
+                                     relu_f(acc[4 * g + 2] + bo.z), relu_f(acc[4 * g + 3] + bo.w));
         if (live) *reinterpret_cast<float4 *>(yp + nb * 32 + 8 * g) = o;
       }
     }
@@ -179,10 +181,10 @@ __global__ __launch_bounds__(kC1Threads) void conv1x1_head_kernel(const float *_
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const float4 b0 = *reinterpret_cast<const float4 *>(&Bo[8 * g + 4 * kh]), b1 = *reinterpret_cast<const float4 *>(&Bo[32 + 8 * g + 4 * kh]);
-        *reinterpret_cast<float4 *>(yp + 8 * g) = make_float4(fmaxf(acc0[4 * g] + b0.x, 0.f), fmaxf(acc0[4 * g + 1] + b0.y, 0.f),
-                                                              fmaxf(acc0[4 * g + 2] + b0.z, 0.f), fmaxf(acc0[4 * g + 3] + b0.w, 0.f));
-        *reinterpret_cast<float4 *>(yp + 32 + 8 * g) = make_float4(fmaxf(acc1[4 * g] + b1.x, 0.f), fmaxf(acc1[4 * g + 1] + b1.y, 0.f),
-                                                                   fmaxf(acc1[4 * g + 2] + b1.z, 0.f), fmaxf(acc1[4 * g + 3] + b1.w, 0.f));
+        *reinterpret_cast<float4 *>(yp + 8 * g) = make_float4(relu_f(acc0[4 * g] + b0.x), relu_f(acc0[4 * g + 1] + b0.y),
+                                                              relu_f(acc0[4 * g + 2] + b0.z), relu_f(acc0[4 * g + 3] + b0.w));
+        *reinterpret_cast<float4 *>(yp + 32 + 8 * g) = make_float4(relu_f(acc1[4 * g] + b1.x), relu_f(acc1[4 * g + 1] + b1.y),
+                                                                   relu_f(acc1[4 * g + 2] + b1.z), relu_f(acc1[4 * g + 3] + b1.w));
       }
     }
   }

@@ -17,6 +17,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "relu_nan.h"
+
 namespace mono {
 
 constexpr int kGnC = 256, kGnG = 32, kGnPix = 64;   // channels, groups, pixels per workgroup
@@ -73,7 +75,10 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float *__restrict__
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.y, g = lane >> 1;
   const double inv_n = 1.0 / (8.0 * HW);
   const double m = stats[((long long)b * kGnG + g) * 2] * inv_n;
-  const double var = fmax(stats[((long long)b * kGnG + g) * 2 + 1] * inv_n - m * m, 0.0);
+  // (negative by rounding only -> 0; NOT fmax, which would turn the NaN of a group holding an Inf (Inf - Inf) into var = 0 and the
+  // group into finite values or -Inf where F.group_norm returns NaN)
+  const double var_raw = stats[((long long)b * kGnG + g) * 2 + 1] * inv_n - m * m;
+  const double var = var_raw < 0.0 ? 0.0 : var_raw;
   const float mean = (float)m, rstd = (float)(1.0 / sqrt(var + (double)eps));
   if (blockIdx.x == 0 && wave == 0 && !(lane & 1)) {
     mean_rstd[((long long)b * kGnG + g) * 2] = mean;
@@ -89,7 +94,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float *__restrict__
     const float4 v = *reinterpret_cast<const float4 *>(x + base + (long long)p * kGnC);
     float4 o = make_float4((v.x + pb.x - mean) * sc.x + be.x, (v.y + pb.y - mean) * sc.y + be.y,
                            (v.z + pb.z - mean) * sc.z + be.z, (v.w + pb.w - mean) * sc.w + be.w);
-    if (RELU) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+    if (RELU) { o.x = relu_f(o.x); o.y = relu_f(o.y); o.z = relu_f(o.z); o.w = relu_f(o.w); }
     *reinterpret_cast<float4 *>(y + base + (long long)p * kGnC) = o;
   }
 }
@@ -113,8 +118,8 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const float *__restri
     v.x += pb.x; v.y += pb.y; v.z += pb.z; v.w += pb.w;
     if (RELU) {
       const float4 yo = *reinterpret_cast<const float4 *>(y + base + (long long)p * kGnC);
-      gv.x = yo.x > 0.f ? gv.x : 0.f; gv.y = yo.y > 0.f ? gv.y : 0.f;
-      gv.z = yo.z > 0.f ? gv.z : 0.f; gv.w = yo.w > 0.f ? gv.w : 0.f;
+      gv.x = relu_on(yo.x) ? gv.x : 0.f; gv.y = relu_on(yo.y) ? gv.y : 0.f;
+      gv.z = relu_on(yo.z) ? gv.z : 0.f; gv.w = relu_on(yo.w) ? gv.w : 0.f;
     }
     a[0] = fma((double)gv.x, (double)((v.x - mean) * rstd), a[0]); a[1] += (double)gv.x;
     a[2] = fma((double)gv.y, (double)((v.y - mean) * rstd), a[2]); a[3] += (double)gv.y;
@@ -192,8 +197,8 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float *__restri
     v.x += pb.x; v.y += pb.y; v.z += pb.z; v.w += pb.w;
     if (RELU) {
       const float4 yo = *reinterpret_cast<const float4 *>(y + base + (long long)p * kGnC);
-      gv.x = yo.x > 0.f ? gv.x : 0.f; gv.y = yo.y > 0.f ? gv.y : 0.f;
-      gv.z = yo.z > 0.f ? gv.z : 0.f; gv.w = yo.w > 0.f ? gv.w : 0.f;
+      gv.x = relu_on(yo.x) ? gv.x : 0.f; gv.y = relu_on(yo.y) ? gv.y : 0.f;
+      gv.z = relu_on(yo.z) ? gv.z : 0.f; gv.w = relu_on(yo.w) ? gv.w : 0.f;
     }
     float4 o;
     o.x = rstd * (gv.x * ga.x - bs - (v.x - mean) * rstd * a);

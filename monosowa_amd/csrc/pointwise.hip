@@ -5,6 +5,7 @@
 // HBM-bound: one read (+ one for the residual) and one write per element, float4 per lane.
 #include <hip/hip_runtime.h>
 
+#include "relu_nan.h"
 #include "groupnorm.hip"
 #include "matched_losses.hip"
 #include "ddn_loss.hip"
@@ -30,7 +31,7 @@ __global__ __launch_bounds__(256) void bias_act_kernel(float *__restrict__ y, co
       const float4 r = reinterpret_cast<const float4 *>(residual)[i];
       v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
     }
-    if (RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+    if (RELU) { v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w); }
     reinterpret_cast<float4 *>(y)[i] = v;
   }
 }
@@ -58,15 +59,15 @@ __global__ __launch_bounds__(256) void bias_relu_maxpool_kernel(const float *__r
         const int ix = 2 * ox - 1 + dx;
         if (ix < 0 || ix >= W) continue;
         const float4 v = reinterpret_cast<const float4 *>(y)[(((long long)n * H + iy) * W + ix) * c_vec + c];
-        m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+        m.x = pool_max(m.x, v.x); m.y = pool_max(m.y, v.y); m.z = pool_max(m.z, v.z); m.w = pool_max(m.w, v.w);
       }
     }
     const float4 b = reinterpret_cast<const float4 *>(bias)[c];
-    reinterpret_cast<float4 *>(out)[i] = make_float4(fmaxf(m.x + b.x, 0.f), fmaxf(m.y + b.y, 0.f), fmaxf(m.z + b.z, 0.f), fmaxf(m.w + b.w, 0.f));
+    reinterpret_cast<float4 *>(out)[i] = make_float4(relu_f(m.x + b.x), relu_f(m.y + b.y), relu_f(m.z + b.z), relu_f(m.w + b.w));
   }
 }
 
-// ReLU variants with a BYTE MASK per float4 (bit k = element k positive): the forward writes 1 B per 16 B of output, the
+// ReLU variants with a BYTE MASK per float4 (bit k = element k positive or NaN): the forward writes 1 B per 16 B of output, the
 // backward reads that instead of y (4 B per element from HBM: y was written long before its backward runs).
 template <bool RES>
 __global__ __launch_bounds__(256) void bias_relu_mask_kernel(float *__restrict__ y, const float *__restrict__ bias,
@@ -81,8 +82,8 @@ __global__ __launch_bounds__(256) void bias_relu_mask_kernel(float *__restrict__
       const float4 r = reinterpret_cast<const float4 *>(residual)[i];
       v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
     }
-    mask[i] = (unsigned char)((v.x > 0.f) | ((v.y > 0.f) << 1) | ((v.z > 0.f) << 2) | ((v.w > 0.f) << 3));
-    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+    mask[i] = (unsigned char)(relu_on(v.x) | (relu_on(v.y) << 1) | (relu_on(v.z) << 2) | (relu_on(v.w) << 3));
+    v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w);
     reinterpret_cast<float4 *>(y)[i] = v;
   }
 }
@@ -128,8 +129,8 @@ __global__ __launch_bounds__(256) void affine_relu_mask_kernel(float *__restrict
     float4 v = reinterpret_cast<float4 *>(y)[i];
     const float4 a = reinterpret_cast<const float4 *>(scale)[i % c_vec], b = reinterpret_cast<const float4 *>(shift)[i % c_vec];
     v.x = v.x * a.x + b.x; v.y = v.y * a.y + b.y; v.z = v.z * a.z + b.z; v.w = v.w * a.w + b.w;
-    mask[i] = (unsigned char)((v.x > 0.f) | ((v.y > 0.f) << 1) | ((v.z > 0.f) << 2) | ((v.w > 0.f) << 3));
-    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+    mask[i] = (unsigned char)(relu_on(v.x) | (relu_on(v.y) << 1) | (relu_on(v.z) << 2) | (relu_on(v.w) << 3));
+    v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w);
     reinterpret_cast<float4 *>(y)[i] = v;
   }
 }
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(256) void affine_relu_grad_kernel(const float *__re
   }
 }
 
-// grad_in = grad_out * (y > 0), optionally also written to a second buffer (the residual branch's gradient)
+// grad_in = grad_out * (y > 0 or NaN), optionally also written to a second buffer (the residual branch's gradient)
 __global__ __launch_bounds__(256) void relu_grad_kernel(const float *__restrict__ grad_out, const float *__restrict__ y,
                                                         float *__restrict__ grad_in, long long n_vec) {
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -153,11 +154,11 @@ __global__ __launch_bounds__(256) void relu_grad_kernel(const float *__restrict_
     const float4 g = reinterpret_cast<const float4 *>(grad_out)[i];
     const float4 v = reinterpret_cast<const float4 *>(y)[i];
     reinterpret_cast<float4 *>(grad_in)[i] =
-        make_float4(v.x > 0.f ? g.x : 0.f, v.y > 0.f ? g.y : 0.f, v.z > 0.f ? g.z : 0.f, v.w > 0.f ? g.w : 0.f);
+        make_float4(relu_on(v.x) ? g.x : 0.f, relu_on(v.y) ? g.y : 0.f, relu_on(v.z) ? g.z : 0.f, relu_on(v.w) ? g.w : 0.f);
   }
 }
 
-// grad_in = scale[channel] * grad_out * (y > 0) on a channels-last tensor (c_vec = C / 4 float4 per pixel): the ReLU backward of a
+// grad_in = scale[channel] * grad_out * (y > 0 or NaN) on a channels-last tensor (c_vec = C / 4 float4 per pixel): the ReLU backward of a
 // trainable 1 x 1 convolution + frozen norm WITHOUT an identity branch, with the norm's scale already on the gradient -- both of its
 // consumers (dX = g' W, dW = g'^T x) then need no scaled copy of the weight / no rescaling of the weight gradient (2 launches per node)
 __global__ __launch_bounds__(256) void relu_grad_scale_kernel(const float *__restrict__ grad_out, const float *__restrict__ y,
@@ -167,12 +168,12 @@ __global__ __launch_bounds__(256) void relu_grad_scale_kernel(const float *__res
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride) {
     const float4 g = reinterpret_cast<const float4 *>(grad_out)[i], v = reinterpret_cast<const float4 *>(y)[i];
     const float4 sc = reinterpret_cast<const float4 *>(scale)[i % c_vec];
-    reinterpret_cast<float4 *>(grad_in)[i] = make_float4(v.x > 0.f ? g.x * sc.x : 0.f, v.y > 0.f ? g.y * sc.y : 0.f,
-                                                         v.z > 0.f ? g.z * sc.z : 0.f, v.w > 0.f ? g.w * sc.w : 0.f);
+    reinterpret_cast<float4 *>(grad_in)[i] = make_float4(relu_on(v.x) ? g.x * sc.x : 0.f, relu_on(v.y) ? g.y * sc.y : 0.f,
+                                                         relu_on(v.z) ? g.z * sc.z : 0.f, relu_on(v.w) ? g.w * sc.w : 0.f);
   }
 }
 
-// grad_in = (grad_a + grad_b) * (y > 0): the two consumers of a block output (next conv and the identity branch) and
+// grad_in = (grad_a + grad_b) * (y > 0 or NaN): the two consumers of a block output (next conv and the identity branch) and
 // the ReLU backward in one pass (autograd would run an accumulation add and then the ReLU backward)
 __global__ __launch_bounds__(256) void relu_grad2_kernel(const float *__restrict__ ga, const float *__restrict__ gb,
                                                          const float *__restrict__ y, float *__restrict__ grad_in, long long n_vec) {
@@ -180,8 +181,8 @@ __global__ __launch_bounds__(256) void relu_grad2_kernel(const float *__restrict
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride) {
     const float4 a = reinterpret_cast<const float4 *>(ga)[i], b = reinterpret_cast<const float4 *>(gb)[i];
     const float4 v = reinterpret_cast<const float4 *>(y)[i];
-    reinterpret_cast<float4 *>(grad_in)[i] = make_float4(v.x > 0.f ? a.x + b.x : 0.f, v.y > 0.f ? a.y + b.y : 0.f,
-                                                         v.z > 0.f ? a.z + b.z : 0.f, v.w > 0.f ? a.w + b.w : 0.f);
+    reinterpret_cast<float4 *>(grad_in)[i] = make_float4(relu_on(v.x) ? a.x + b.x : 0.f, relu_on(v.y) ? a.y + b.y : 0.f,
+                                                         relu_on(v.z) ? a.z + b.z : 0.f, relu_on(v.w) ? a.w + b.w : 0.f);
   }
 }
 
@@ -193,8 +194,8 @@ __global__ __launch_bounds__(256) void relu_grad3_kernel(const float *__restrict
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride) {
     const float4 a = reinterpret_cast<const float4 *>(ga)[i], b = reinterpret_cast<const float4 *>(gb)[i], c = reinterpret_cast<const float4 *>(gc)[i];
     const float4 v = reinterpret_cast<const float4 *>(y)[i];
-    reinterpret_cast<float4 *>(grad_in)[i] = make_float4(v.x > 0.f ? (a.x + b.x) + c.x : 0.f, v.y > 0.f ? (a.y + b.y) + c.y : 0.f,
-                                                         v.z > 0.f ? (a.z + b.z) + c.z : 0.f, v.w > 0.f ? (a.w + b.w) + c.w : 0.f);
+    reinterpret_cast<float4 *>(grad_in)[i] = make_float4(relu_on(v.x) ? (a.x + b.x) + c.x : 0.f, relu_on(v.y) ? (a.y + b.y) + c.y : 0.f,
+                                                         relu_on(v.z) ? (a.z + b.z) + c.z : 0.f, relu_on(v.w) ? (a.w + b.w) + c.w : 0.f);
   }
 }
 
@@ -288,17 +289,17 @@ __global__ __launch_bounds__(256) void dropout_add_ln_bwd_kernel(
 }
 
 // ---- y = dropout(relu(h)) (FFN hidden activation, depthaware_transformer.py:352 `self.dropout2(F.relu(self.linear1(src)))`)
-// forward: one pass, hash mask; backward: grad_h = grad_y * scale where y > 0 (y > 0 <=> kept and h > 0), zero elsewhere
+// forward: one pass, hash mask; backward: grad_h = grad_y * scale where y > 0 or y is NaN (y > 0 <=> kept and h > 0), zero elsewhere
 __global__ __launch_bounds__(256) void relu_dropout_fwd_kernel(const float *__restrict__ h, float *__restrict__ y, long long n_vec,
                                                                unsigned threshold, float scale, unsigned long long seed) {
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride) {
     float4 v = reinterpret_cast<const float4 *>(h)[i];
     const long long e = i * 4;
-    v.x = v.x > 0.f ? v.x * keep_scale(seed, e, threshold, scale) : 0.f;
-    v.y = v.y > 0.f ? v.y * keep_scale(seed, e + 1, threshold, scale) : 0.f;
-    v.z = v.z > 0.f ? v.z * keep_scale(seed, e + 2, threshold, scale) : 0.f;
-    v.w = v.w > 0.f ? v.w * keep_scale(seed, e + 3, threshold, scale) : 0.f;
+    v.x = relu_on(v.x) ? v.x * keep_scale(seed, e, threshold, scale) : 0.f;
+    v.y = relu_on(v.y) ? v.y * keep_scale(seed, e + 1, threshold, scale) : 0.f;
+    v.z = relu_on(v.z) ? v.z * keep_scale(seed, e + 2, threshold, scale) : 0.f;
+    v.w = relu_on(v.w) ? v.w * keep_scale(seed, e + 3, threshold, scale) : 0.f;
     reinterpret_cast<float4 *>(y)[i] = v;
   }
 }
@@ -307,8 +308,8 @@ __global__ __launch_bounds__(256) void relu_dropout_bwd_kernel(const float *__re
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride) {
     const float4 g = reinterpret_cast<const float4 *>(gy)[i], v = reinterpret_cast<const float4 *>(y)[i];
-    reinterpret_cast<float4 *>(gh)[i] = make_float4(v.x > 0.f ? g.x * scale : 0.f, v.y > 0.f ? g.y * scale : 0.f,
-                                                    v.z > 0.f ? g.z * scale : 0.f, v.w > 0.f ? g.w * scale : 0.f);
+    reinterpret_cast<float4 *>(gh)[i] = make_float4(relu_on(v.x) ? g.x * scale : 0.f, relu_on(v.y) ? g.y * scale : 0.f,
+                                                    relu_on(v.z) ? g.z * scale : 0.f, relu_on(v.w) ? g.w * scale : 0.f);
   }
 }
 
@@ -324,8 +325,8 @@ __global__ __launch_bounds__(256) void relu_dropout_bwd_colsum_kernel(const floa
   for (long long r = (long long)blockIdx.x * 4 + wave; r < rows; r += wave_stride) {
     const long long e = r * 256 + lane * 4;
     const float4 g = *reinterpret_cast<const float4 *>(gy + e), v = *reinterpret_cast<const float4 *>(y + e);
-    const float4 o = make_float4(v.x > 0.f ? g.x * scale : 0.f, v.y > 0.f ? g.y * scale : 0.f, v.z > 0.f ? g.z * scale : 0.f,
-                                 v.w > 0.f ? g.w * scale : 0.f);
+    const float4 o = make_float4(relu_on(v.x) ? g.x * scale : 0.f, relu_on(v.y) ? g.y * scale : 0.f, relu_on(v.z) ? g.z * scale : 0.f,
+                                 relu_on(v.w) ? g.w * scale : 0.f);
     *reinterpret_cast<float4 *>(gh + e) = o;
     acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w;
   }
@@ -723,7 +724,8 @@ int mono_bias_relu_maxpool_nhwc_f32(const float *y, const float *bias, float *ou
 }
 
 // Y[M, 256] = relu(relu(X[M, 64] + b_in) W[64, 256] + b_out + R[M, 256]): the tail of a frozen bottleneck in one pass (conv1x1_fused.hip).
-// Rows are channels-last pixels; w is [K][N] (the 1 x 1 convolution's weight, transposed, norm scale folded in).  y may be res.
+// Rows are channels-last pixels; w is [K][N] (the 1 x 1 convolution's weight, transposed, norm scale folded in).  y must be a buffer of its
+// own: y == res and y == x are refused with -2 (the kernel reads res a channel block ahead of its stores to y).
 int mono_conv1x1_tail_f32(const float *x, const float *b_in, const float *w, const float *b_out, const float *res, float *y,
                           long long M, int K, int N, void *stream_) {
   if (!x || !b_in || !w || !b_out || !res || !y) return -1;
@@ -835,7 +837,7 @@ int mono_relu_grad_f32(const float *grad_out, const float *y, float *grad_in, lo
   return (int)hipGetLastError();
 }
 
-// grad_in = scale[c] * grad_out * (y > 0), channels-last [.., C] with n elements in all; C % 4 == 0, n % C == 0.
+// grad_in = scale[c] * grad_out * (y > 0 or NaN), channels-last [.., C] with n elements in all; C % 4 == 0, n % C == 0.
 int mono_relu_grad_scale_f32(const float *grad_out, const float *y, const float *scale, float *grad_in, long long n, int C, void *stream_) {
   if (!grad_out || !y || !scale || !grad_in) return -1;
   if (n <= 0 || C <= 0 || (C & 3) || n % C || ((uintptr_t)grad_out & 15) || ((uintptr_t)y & 15) || ((uintptr_t)grad_in & 15) || ((uintptr_t)scale & 15))
@@ -886,7 +888,7 @@ int mono_relu_dropout_fwd_f32(const float *h, float *y, long long n, float p, un
   return (int)hipGetLastError();
 }
 
-// grad_h = grad_y / (1 - p) where y > 0, else 0  (y = the forward output).
+// grad_h = grad_y / (1 - p) where y > 0 or y is NaN, else 0  (y = the forward output).
 int mono_relu_dropout_bwd_f32(const float *grad_y, const float *y, float *grad_h, long long n, float p, void *stream_) {
   if (!grad_y || !y || !grad_h) return -1;
   if (n <= 0 || (n & 3) || !(p >= 0.f && p < 1.f) || ((uintptr_t)grad_y & 15) || ((uintptr_t)y & 15) || ((uintptr_t)grad_h & 15)) return -2;

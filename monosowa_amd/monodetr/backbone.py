@@ -151,7 +151,7 @@ class _Conv1x1BnAct(torch.autograd.Function):
         # Without an identity branch and with one consumer (conv1 of a bottleneck) the norm's scale goes onto the gradient inside the
         # ReLU backward's pass: dX = g' w and dW = g'^T x need neither a scaled copy of the weight nor a rescaled weight gradient.
         pre_scaled = bool(CONV1X1_SCALED_GRAD) and not ctx.has_res and len(given) == 1 and scale.data_ptr() % 16 == 0 and scale.is_contiguous()
-        g = relu_grad_from_output(given, y, scale if pre_scaled else None)         # (sum of the consumers' gradients) * (y > 0), one pass
+        g = relu_grad_from_output(given, y, scale if pre_scaled else None)         # (sum of the consumers' gradients) * (y > 0 or NaN), one pass
         gx = gw = None
         w2 = w.reshape(K, C)
         if ctx.needs_input_grad[0]:

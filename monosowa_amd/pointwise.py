@@ -280,7 +280,7 @@ class _BiasActFork(torch.autograd.Function):
 
 
 def relu_grad_from_output(grads, y, scale=None):
-    """``(sum of grads) * (y > 0)`` for the 1 - 3 gradients a ReLU output's consumers returned, in ONE pass that reads the mask off
+    """``(sum of grads) * (y > 0 or NaN)`` for the 1 - 3 gradients a ReLU output's consumers returned, in ONE pass that reads the mask off
     the output itself (channels-last float32; the epilogue-GEMM bottleneck paths of backbone.py keep no byte mask).
     ``scale`` (one gradient only): a per-channel factor put on the result in the same pass."""
     cl = lambda t: t.contiguous(memory_format=torch.channels_last)
