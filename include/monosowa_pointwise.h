@@ -126,6 +126,12 @@ int mono_grad_guard_f32(const void *const *tables, const int *n_chunks, int n_gr
 int mono_adamw_step_guarded_f32(const void *table, int n_chunks, double beta1, double beta2, double eps, double step_size,
                                 const void *record, void *stream);
 
+/* Gradient accumulation over the micro-batches of one optimizer step: acc[i] += g[i] (one correctly rounded f32 add per element, the
+ * bits of torch's in-place add) for all parameters in one launch.  table (device): acc[n_chunks], g[n_chunks] as 64-bit device
+ * addresses (4-byte aligned at least; 16-byte aligned pairs take the float4 path), then n[n_chunks] (int32 elements per chunk, any
+ * size).  Exactly the elements [0, n) of every chunk are written. */
+int mono_grad_accumulate_f32(const void *table, int n_chunks, void *stream);
+
 /* dW[M, N] = dY[R, M]^T . X[R, N] and (db != NULL) db[M] = the column sums of dY, f32, exact products (v_mfma_f32_32x32x2_f32), summed in a
  * fixed order (no atomics): the weight and bias gradients of y = x W^T + b over a few thousand tokens -- autograd's AddmmBackward of the
  * nn.Linear layers of the decoder / depth-token encoder (reference depthaware_transformer.py:339-354,440-515) -- in two launches that

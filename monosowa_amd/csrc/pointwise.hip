@@ -677,6 +677,30 @@ __global__ __launch_bounds__(256) void grad_guard_fold_kernel(const double *__re
   }
 }
 
+// ---- gradient accumulation over micro-batches: acc += g for every parameter in ONE launch ------------------------------------------
+// One workgroup per chunk (<= 32768 elements of one tensor) of a table {accumulator address, gradient address, count}: what
+// autograd's AccumulateGrad does with one in-place add per parameter.  One correctly rounded float32 add per element, so the bits
+// are those of torch's add_.  float4 path when both pointers are 16-byte aligned; only elements [0, n) of a chunk are touched.
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(const unsigned long long *__restrict__ ap, const unsigned long long *__restrict__ gp,
+                                                              const int *__restrict__ ns) {
+  const int c = blockIdx.x;
+  float *a = reinterpret_cast<float *>(ap[c]);
+  const float *g = reinterpret_cast<const float *>(gp[c]);
+  const int n = ns[c];
+  if (((ap[c] | gp[c]) & 15ull) == 0) {
+    const int n4 = n >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      float4 A = reinterpret_cast<float4 *>(a)[i];
+      const float4 G = reinterpret_cast<const float4 *>(g)[i];
+      A.x = __fadd_rn(A.x, G.x); A.y = __fadd_rn(A.y, G.y); A.z = __fadd_rn(A.z, G.z); A.w = __fadd_rn(A.w, G.w);
+      reinterpret_cast<float4 *>(a)[i] = A;
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) a[i] = __fadd_rn(a[i], g[i]);
+  } else {
+    for (int i = threadIdx.x; i < n; i += 256) a[i] = __fadd_rn(a[i], g[i]);
+  }
+}
+
 inline int grid_for_vec(long long n_vec) {
   long long g = (n_vec + 255) / 256;
   if (g > 256LL * 32) g = 256LL * 32;
@@ -965,6 +989,17 @@ int mono_adamw_step_guarded_f32(const void *table, int n_chunks, double beta1, d
                                 const void *record, void *stream_) {
   if (!record) return -1;
   return adamw_launch(table, n_chunks, beta1, beta2, eps, step_size, record, stream_);
+}
+
+// acc += g over n_chunks chunks (gradient accumulation over the micro-batches of one optimizer step).  table: device buffer holding,
+// back to back, acc[n_chunks], g[n_chunks] (64-bit device addresses, 4-byte aligned at least), n[n_chunks] (int32, elements per chunk).
+int mono_grad_accumulate_f32(const void *table, int n_chunks, void *stream_) {
+  if (!table) return -1;
+  if (n_chunks <= 0) return -2;
+  const unsigned long long *ap = reinterpret_cast<const unsigned long long *>(table);
+  const int *ns = reinterpret_cast<const int *>(ap + 2 * (size_t)n_chunks);
+  mono::grad_accumulate_kernel<<<n_chunks, 256, 0, (hipStream_t)stream_>>>(ap, ap + n_chunks, ns);
+  return (int)hipGetLastError();
 }
 
 // Global L2 norm of the gradients of n_groups chunk tables (the layout of mono_adamw_step_f32; the g and n columns are read) and the

@@ -9,7 +9,11 @@ checkpoint naming.  Differences that do not change results:
 * with ``optimizer.clip_max_norm`` / ``optimizer.skip_nonfinite`` configured (optimizer_helper.py) the logging iterations
   also print the gradient norm and the number of skipped steps, and an epoch in which EVERY step was skipped raises
   instead of writing a checkpoint; without the keys the printed lines are the reference's.
+* ``trainer.global_batch: N`` (optional, absent from the shipped config): N images per optimizer step whatever the number of
+  GPUs, by gradient accumulation over K = N / (world size * per-GPU batch) loader batches -- one *cycle*.  A cycle is, by
+  definition, one DDP step of K * W ranks: see ``Trainer.train_cycle``.  Absent, 0 or K = 1: the loop below is the plain one.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -99,6 +103,8 @@ class Trainer(object):
         self.tester = None
         self.log_interval = 30
         self._guard_skipped = 0          # optimizer.guard_report()["skipped_total"] at the end of the previous epoch
+        self.accum_steps = self._accum_steps(cfg.get("global_batch"), train_loader)      # K: loader batches per optimizer step
+        self._accumulator = None
 
         if cfg.get("pretrain_model"):
             assert os.path.exists(cfg["pretrain_model"])
@@ -166,6 +172,76 @@ class Trainer(object):
         self.optimizer.step()
         return total, loss_dict
 
+    @staticmethod
+    def _accum_steps(global_batch, train_loader):
+        """K of ``trainer.global_batch: N``: N / (W * b), W the world size and b the loader's per-GPU batch size; 1 without the key."""
+        if not global_batch:             # absent, None or 0: off
+            return 1
+        world, per_gpu = misc.get_world_size(), getattr(train_loader, "batch_size", None)
+        ok = isinstance(global_batch, int) and not isinstance(global_batch, bool) and isinstance(per_gpu, int) and per_gpu > 0 \
+            and global_batch > 0 and global_batch % (world * per_gpu) == 0
+        if not ok:
+            raise ValueError("trainer.global_batch = %r is not a positive multiple of world size x per-GPU batch size = %r x %r"
+                             % (global_batch, world, per_gpu))
+        return global_batch // (world * per_gpu)
+
+    @staticmethod
+    def _host_box_count(raw):
+        """Boxes of one collated loader batch, from the object mask on the host (no device synchronisation)."""
+        mask = raw[2]["mask_2d"]
+        host = getattr(mask, "_host_mask", None)
+        if host is None:
+            if mask.is_cuda:
+                raise ValueError("gradient accumulation counts the boxes of a cycle on the host: a device-resident batch needs "
+                                 "synthetic.attach_host_mask on its mask_2d")
+            host = mask.numpy()
+        return int(np.count_nonzero(host))
+
+    def _cycle_num_boxes(self, n_boxes, micro_steps):
+        """The criterion's normaliser for every micro-batch of a cycle with ``n_boxes`` boxes on this rank:
+        max(job-wide boxes * group_num / (K * W), 1) -- ``SetCriterion._num_boxes`` with K * W in place of the world size."""
+        group_num = self.detr_loss.group_num if self.detr_loss.training else 1
+        n = float(n_boxes * group_num)
+        ranks = micro_steps * misc.get_world_size()
+        if misc.is_dist_avail_and_initialized():           # one all-reduce per cycle, on the device: no sync
+            t = torch.as_tensor(np.asarray([n])).to(torch.float).to(self.device, non_blocking=True)
+            torch.distributed.all_reduce(t)
+            return torch.clamp(t / ranks, min=1)[0]
+        return max(n / ranks, 1.0)
+
+    def train_cycle(self, raws):
+        """One optimizer step over the K = len(raws) collated loader batches of a cycle; returns the last micro-batch's (total loss
+        tensor, loss dict).  Defined as one DDP step of K * W ranks (W the world size), rank by rank: every micro-batch has its own
+        forward (its own matching and size compensation) and is normalised by the box count of the whole cycle over all ranks,
+        max(n * group_num / (K * W), 1); its weighted loss enters with 1 / K, which is DDP's gradient mean.  The gradients add up in
+        micro-batch order, one float32 add per element and micro-step; the optimizer (and its guard) sees the sum once.  Under DDP
+        only the last backward all-reduces.  The staged copy of a batch lives for its own micro-step only."""
+        K = len(raws)
+        if K == 1:                                         # the tail of an epoch: exactly a plain step
+            return self.train_step(*stage_batch(raws[0], self.device))
+        num_boxes = self._cycle_num_boxes(sum(self._host_box_count(raw) for raw in raws), K)
+        ddp = isinstance(self.model, torch.nn.parallel.DistributedDataParallel)
+        if self._accumulator is None:
+            from ..pointwise import GradAccumulator
+            # DDP's gradients are views of its buckets: there autograd adds in place, inside no_sync()
+            self._accumulator = GradAccumulator([p for g in self.optimizer.param_groups for p in g["params"]], fused=not ddp)
+        acc = self._accumulator
+        acc.begin()
+        weight_dict = self.detr_loss.weight_dict
+        self.optimizer.zero_grad(set_to_none=True)
+        for k, raw in enumerate(raws):
+            inputs, calibs, targets, info = stage_batch(raw, self.device)
+            target_list = self.prepare_targets(targets, inputs.shape[0])
+            with (self.model.no_sync() if ddp and k < K - 1 else contextlib.nullcontext()):
+                outputs = self.model(inputs, calibs, target_list, targets["img_size"], dn_args=None)
+                loss_dict = self.detr_loss(outputs, target_list, None, info, num_boxes=num_boxes)
+                total = weighted_total(loss_dict, weight_dict) / K
+                total.backward()
+            acc.collect(k)
+        acc.install()
+        self.optimizer.step()
+        return total, loss_dict
+
     def train_one_epoch(self, epoch):
         torch.set_grad_enabled(True)
         self.model.train()
@@ -175,13 +251,31 @@ class Trainer(object):
             print(">>>>>>> Epoch:", str(epoch) + ":")
         bar = tqdm.tqdm(total=len(self.train_loader), leave=(self.epoch + 1 == self.cfg["max_epoch"]), desc="iters", disable=not main)
         steps = 0
-        for batch_idx, raw in enumerate(self.train_loader):
-            inputs, calibs, targets, info = stage_batch(raw, self.device)
-            total, loss_dict = self.train_step(inputs, calibs, targets, info)
-            steps += 1
-            if batch_idx % self.log_interval == 0:
-                self._log(batch_idx, loss_dict)
-            bar.update()
+        if self.accum_steps > 1:
+            raws = []
+
+            def cycle():
+                nonlocal steps, raws
+                total, loss_dict = self.train_cycle(raws)
+                if steps % self.log_interval == 0:             # every log_interval-th optimizer step
+                    self._log(steps, loss_dict)
+                steps += 1
+                bar.update(len(raws))
+                raws = []
+            for raw in self.train_loader:
+                raws.append(raw)                           # collated batches wait on the host; one at a time is staged
+                if len(raws) == self.accum_steps:
+                    cycle()
+            if raws:                                       # the epoch's tail: len(loader) mod K micro-batches
+                cycle()
+        else:
+            for batch_idx, raw in enumerate(self.train_loader):
+                inputs, calibs, targets, info = stage_batch(raw, self.device)
+                total, loss_dict = self.train_step(inputs, calibs, targets, info)
+                steps += 1
+                if batch_idx % self.log_interval == 0:
+                    self._log(batch_idx, loss_dict)
+                bar.update()
         bar.close()
         # the device assignment solver reports an invalid cost matrix through a status word (no exception from a kernel, no wait in
         # the step): look at it for certain before the epoch's checkpoint is written

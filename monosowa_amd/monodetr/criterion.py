@@ -263,10 +263,12 @@ class SetCriterion(nn.Module):
         assert loss in loss_map, f"do you really want to compute {loss} loss?"
         return loss_map[loss](outputs, targets, indices, num_boxes, **kwargs)
 
-    def forward(self, outputs, targets, mask_dict=None, info=None):
+    def forward(self, outputs, targets, mask_dict=None, info=None, num_boxes=None):
+        """``num_boxes`` (a float or a 0-d device tensor): the normaliser to use in place of this forward's own box count, already
+        job-wide -- nothing is all-reduced then.  The Trainer's gradient accumulation passes the cycle-wide count."""
         if self.fast:
-            return self.forward_fast(outputs, targets)
-        return self.forward_layerwise(outputs, targets, mask_dict, info)
+            return self.forward_fast(outputs, targets, num_boxes)
+        return self.forward_layerwise(outputs, targets, mask_dict, info, num_boxes)
 
     # ------------------------------------------------------------------ batched formulation
     def _num_boxes(self, targets, group_num, device):
@@ -277,7 +279,7 @@ class SetCriterion(nn.Module):
             return torch.clamp(t / get_world_size(), min=1)[0]
         return max(n / get_world_size(), 1.0)
 
-    def forward_fast(self, outputs, targets):
+    def forward_fast(self, outputs, targets, num_boxes=None):
         """Same losses as ``forward_layerwise`` (same keys, same normalisation); the matching of all decoder
         layers is one cost pass + one host copy + one native call, and every loss is evaluated for all layers
         at once through flat (layer, batch, query) / target index tensors."""
@@ -297,7 +299,8 @@ class SetCriterion(nn.Module):
         flat = getattr(targets, "flat", None)              # prepare_targets hands the batch-flat tensors along (7 launches fewer)
         if flat is None or any(k not in flat for k in flat_keys) or flat["labels"].shape[0] != T:
             flat = {k: torch.cat([t[k] for t in targets], dim=0) for k in flat_keys}
-        num_boxes = self._num_boxes(targets, group_num, dev)
+        if num_boxes is None:
+            num_boxes = self._num_boxes(targets, group_num, dev)
 
         pending = self.matcher.match_layers_begin(logits, boxes, flat, sizes, group_num)      # cost pass + async D2H
 
@@ -433,16 +436,17 @@ class SetCriterion(nn.Module):
         return losses
 
     # ------------------------------------------------------------------ reference formulation
-    def forward_layerwise(self, outputs, targets, mask_dict=None, info=None):
+    def forward_layerwise(self, outputs, targets, mask_dict=None, info=None, num_boxes=None):
         outputs_without_aux = {k: v for k, v in outputs.items() if k != "aux_outputs"}
         group_num = self.group_num if self.training else 1
         indices = self.matcher(outputs_without_aux, targets, group_num=group_num)
 
-        num_boxes = sum(len(t["labels"]) for t in targets) * group_num
-        num_boxes = torch.as_tensor([num_boxes], dtype=torch.float, device=next(iter(outputs.values())).device)
-        if is_dist_avail_and_initialized():
-            torch.distributed.all_reduce(num_boxes)
-        num_boxes = torch.clamp(num_boxes / get_world_size(), min=1).item()
+        if num_boxes is None:
+            num_boxes = sum(len(t["labels"]) for t in targets) * group_num
+            num_boxes = torch.as_tensor([num_boxes], dtype=torch.float, device=next(iter(outputs.values())).device)
+            if is_dist_avail_and_initialized():
+                torch.distributed.all_reduce(num_boxes)
+            num_boxes = torch.clamp(num_boxes / get_world_size(), min=1).item()
 
         losses = {}
         for loss in self.losses:

@@ -15,7 +15,7 @@ SYMBOLS = ("mono_bias_act_f32", "mono_bias_relu_maxpool_nhwc_f32", "mono_conv1x1
            "mono_relu_dropout_bwd_f32", "mono_matched_losses_fwd_f32", "mono_matched_losses_bwd_f32", "mono_ddn_loss_blocks",
            "mono_ddn_loss_fwd_f32", "mono_ddn_loss_bwd_f32", "mono_depth_expect_fwd_f32", "mono_depth_expect_bwd_f32", "mono_focal_fwd_f32", "mono_focal_bwd_f32", "mono_head_tail_fwd_f32", "mono_head_tail_bwd_f32", "mono_match_cost_f32", "mono_refine_reference_f32", "mono_relu_dropout_bwd_colsum_f32", "mono_sum_slices_f32", "mono_colsum_any_blocks", "mono_colsum_any_f32", "mono_relu_grad_mask3_f32", "mono_lsap_match_flat_f32",
            "mono_linear_wgrad_workspace", "mono_linear_wgrad_f32", "mono_colsum_levels_blocks", "mono_colsum_levels_f32", "mono_relu_grad_scale_f32",
-           "mono_set_deterministic", "mono_groupnorm_stats_doubles", "mono_groupnorm_part_doubles")
+           "mono_set_deterministic", "mono_groupnorm_stats_doubles", "mono_groupnorm_part_doubles", "mono_grad_accumulate_f32")
 _lib = None
 
 
@@ -96,6 +96,8 @@ def load():
         lib.mono_adamw_step_guarded_f32.argtypes = [P, I] + [ctypes.c_double] * 4 + [P, P]
         lib.mono_grad_guard_f32.restype = I
         lib.mono_grad_guard_f32.argtypes = [P, P, I, ctypes.c_float, I, P, P, P]
+        lib.mono_grad_accumulate_f32.restype = I
+        lib.mono_grad_accumulate_f32.argtypes = [P, I, P]
         lib.mono_colsum_strided_f32.restype = I
         lib.mono_colsum_strided_f32.argtypes = [P, P, P, I, LL, LL, I, P]
         lib.mono_colsum_levels_blocks.restype = I
@@ -855,6 +857,115 @@ class GradGuard:
         raw = self.record.cpu().numpy().view(np.uint8)
         return {"grad_norm": float(raw[0:4].view(np.float32)[0]), "coef": float(raw[4:8].view(np.float32)[0]),
                 "skip": int(raw[8:12].view(np.int32)[0]), "skipped_total": int(raw[16:24].view(np.int64)[0])}
+
+
+FUSED_ACCUMULATE = True       # gradient accumulation over micro-batches through mono_grad_accumulate_f32 (False: autograd's in-place adds)
+
+
+def accumulate_supported(params, grads):
+    """What ``AdamW._fused_plan`` asks of a parameter and its gradient: dense float32 GPU tensors of one layout, on one device."""
+    def dense(t):
+        return t.is_cuda and t.dtype == torch.float32 and (t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)))
+    return bool(params) and all(dense(p) and dense(g) and p.stride() == g.stride() and p.shape == g.shape and g.device == params[0].device
+                                for p, g in zip(params, grads))
+
+
+class GradAccumulatePlan:
+    """Chunk table of ``mono_grad_accumulate_f32`` over ALL parameters that take part in a gradient-accumulation cycle (every group
+    in one launch): the split into chunks is fixed by the parameter sizes, the two address columns are written per call (both the
+    accumulators -- micro-step 0's gradient tensors -- and the fresh gradients are re-allocated) and shipped like
+    ``FusedAdamWPlan.refresh`` ships its table."""
+
+    def __init__(self, params):
+        sizes = np.array([p.numel() for p in params], dtype=np.int64)
+        per = (sizes + ADAM_CHUNK - 1) // ADAM_CHUNK
+        self.tensor = np.repeat(np.arange(len(params)), per)
+        first = np.cumsum(per) - per
+        self.offset = ((np.arange(per.sum()) - np.repeat(first, per)) * ADAM_CHUNK * 4).astype(np.uint64)      # bytes
+        self.n_chunks = int(per.sum())
+        self.sizes = sizes
+        self.device = params[0].device
+        nbytes = self.n_chunks * (2 * 8 + 4)
+        self.host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        view = self.host.numpy()
+        self.cols = view[:self.n_chunks * 16].view(np.uint64).reshape(2, self.n_chunks)
+        view[self.n_chunks * 16:].view(np.int32)[:] = np.minimum(sizes[self.tensor] - self.offset.astype(np.int64) // 4, ADAM_CHUNK)
+        self.copied = None
+
+    def matches(self, params):
+        return len(params) == len(self.sizes) and params[0].device == self.device and all(p.numel() == n for p, n in zip(params, self.sizes))
+
+    def add(self, accs, grads, checked=False):
+        """accs[i] += grads[i], element-wise over storage order, in one launch; nothing waits for the device.  ``checked``: the caller
+        has already asked ``accumulate_supported(accs, grads)``."""
+        if not (self.matches(accs) and self.matches(grads) and (checked or accumulate_supported(accs, grads))):      # the table's counts bound every access
+            raise ValueError("GradAccumulatePlan.add: tensors do not match the plan (count, sizes, device, dense float32 layout)")
+        ptr = lambda ts: np.array([t.data_ptr() for t in ts], dtype=np.uint64)
+        if self.copied is not None:
+            self.copied.synchronize()                     # the previous call's table copy has left the pinned buffer
+        self.cols[0] = ptr(accs)[self.tensor] + self.offset
+        self.cols[1] = ptr(grads)[self.tensor] + self.offset
+        with on_device(self.device):
+            self.dev.copy_(self.host, non_blocking=True)
+            self.copied = torch.cuda.Event()
+            self.copied.record()
+            code = load().mono_grad_accumulate_f32(self.dev.data_ptr(), self.n_chunks, raw_stream())
+        if code:
+            raise RuntimeError("mono_grad_accumulate_f32 failed with code %d" % code)
+
+
+class GradAccumulator:
+    """Gradient accumulation over the micro-batches of one optimizer step.  ``collect()`` is called after every backward.  Kernel
+    path (``FUSED_ACCUMULATE``, dense float32 GPU gradients in their parameters' layout, ``fused`` not refused by the caller):
+    micro-step 0's ``.grad`` tensors BECOME the accumulators (no copy), every later micro-step's fresh gradients are added by one
+    ``mono_grad_accumulate_f32`` launch, ``.grad`` is ``None`` in between and ``install()`` puts the accumulators back before the
+    optimizer steps.  Otherwise ``.grad`` is left where it is and autograd adds into it in place; a cycle that meets a tensor the
+    kernel does not take at a LATER micro-step (a first gradient or a fresh gradient in another layout) goes over to autograd's adds
+    there and then, without an exception.  Both compute fl(acc + g) per element in micro-batch order: the same bits."""
+
+    def __init__(self, params, fused=True):
+        self.params = [p for p in params if p.requires_grad]
+        self.fused = fused
+        self.plan = None
+        self.acc = None                # {parameter index: accumulator} while a cycle is open on the kernel path
+
+    def begin(self):
+        self.acc = None
+
+    def collect(self, micro_step):
+        have = [(i, p) for i, p in enumerate(self.params) if p.grad is not None]
+        if micro_step == 0:
+            ok = self.fused and FUSED_ACCUMULATE and accumulate_supported([p for _, p in have], [p.grad for _, p in have])
+            self.acc = {} if ok else None
+        if self.acc is None:
+            return
+        add = [(i, p) for i, p in have if i in self.acc]
+        new = [p for i, p in have if i not in self.acc]
+        if micro_step and ((add and not accumulate_supported([self.acc[i] for i, _ in add], [p.grad for _, p in add]))
+                           or (new and not accumulate_supported(new, [p.grad for p in new]))):
+            # the rest of the cycle through autograd: this micro-step's gradients added by torch (the same fl(acc + g)), the
+            # accumulators back in .grad, where the next backward adds in place
+            with torch.no_grad():
+                for i, p in add:
+                    self.acc[i].add_(p.grad)
+            self.install()
+            return
+        if add:
+            ps = [p for _, p in add]
+            if self.plan is None or not self.plan.matches(ps):
+                self.plan = GradAccumulatePlan(ps)
+            self.plan.add([self.acc[i] for i, _ in add], [p.grad for _, p in add], checked=micro_step > 0)
+        for i, p in have:
+            if i not in self.acc:
+                self.acc[i] = p.grad          # first gradient of this parameter in the cycle: it is the accumulator
+            p.grad = None
+
+    def install(self):
+        if self.acc is not None:
+            for i, g in self.acc.items():
+                self.params[i].grad = g
+            self.acc = None
 
 
 # ---------------------------------------------------------------------------------------------------------
