@@ -132,6 +132,16 @@ int mono_adamw_step_guarded_f32(const void *table, int n_chunks, double beta1, d
  * size).  Exactly the elements [0, n) of every chunk are written. */
 int mono_grad_accumulate_f32(const void *table, int n_chunks, void *stream);
 
+/* Exponential moving average of the weights, its own launch behind the optimizer step: e[i] += w * (p[i] - e[i]) for all tracked
+ * parameters in one launch.  Three float32 roundings per element, in this order and never contracted to an FMA, so numpy in float32
+ * gives the same bits:  d = p - e;  t = w * d;  e' = e + t.  NaN and +-Inf propagate as those three IEEE operations do.
+ * table (device): e[n_chunks], p[n_chunks] as 64-bit device addresses (4-byte aligned at least; 16-byte aligned pairs take the float4
+ * path), then n[n_chunks] (int32 elements per chunk, any size) -- the layout of mono_grad_accumulate_f32's table.  Exactly the elements
+ * [0, n) of every chunk are written; p is read only.  record: NULL, or the guard record mono_grad_guard_f32 wrote earlier on the same
+ * stream: with its skip field set nothing is stored (every byte of e keeps its value), like mono_adamw_step_guarded_f32.
+ * Returns -1 for a NULL table, -2 for n_chunks < 0; n_chunks == 0 launches nothing and returns 0. */
+int mono_ema_update_f32(const void *table, int n_chunks, float w, const void *record, void *stream);
+
 /* dW[M, N] = dY[R, M]^T . X[R, N] and (db != NULL) db[M] = the column sums of dY, f32, exact products (v_mfma_f32_32x32x2_f32), summed in a
  * fixed order (no atomics): the weight and bias gradients of y = x W^T + b over a few thousand tokens -- autograd's AddmmBackward of the
  * nn.Linear layers of the decoder / depth-token encoder (reference depthaware_transformer.py:339-354,440-515) -- in two launches that

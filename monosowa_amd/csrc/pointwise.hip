@@ -701,6 +701,41 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(const unsigned lon
   }
 }
 
+// ---- exponential moving average of the weights: e += w * (p - e) for every tracked parameter in ONE launch -------------------------------
+// One workgroup per chunk (<= 32768 elements of one tensor) of a table {average address, parameter address, count}, the layout and the
+// occupancy of grad_accumulate_kernel (12 bytes per element: two loads, one store).  Three float32 roundings per element, in this order and
+// never contracted (hipcc's default is -ffp-contract=fast and the "_rn" intrinsics are plain operators, see msda_common.h; the pragma takes
+// the `contract` flag off these operations themselves), so numpy in float32 reproduces the bits:  d = p - e;  t = w * d;  e' = e + t.
+// NaN and +-Inf come out as those three IEEE operations give them.  rec != nullptr and rec->skip set (the guard record of this step, written
+// earlier on the stream): nothing is stored, like adamw_kernel.  Only elements [0, n) of a chunk are written; p is read only.
+__device__ __forceinline__ float ema_one(float e, float p, float w) {
+#pragma clang fp contract(off)
+  const float d = p - e;
+  const float t = w * d;
+  return e + t;
+}
+
+__global__ __launch_bounds__(256) void ema_update_kernel(const unsigned long long *__restrict__ ep, const unsigned long long *__restrict__ pp,
+                                                         const int *__restrict__ ns, float w, const GuardRecord *__restrict__ rec) {
+  if (rec != nullptr && rec->skip) return;
+  const int c = blockIdx.x;
+  float *e = reinterpret_cast<float *>(ep[c]);
+  const float *p = reinterpret_cast<const float *>(pp[c]);
+  const int n = ns[c];
+  if (((ep[c] | pp[c]) & 15ull) == 0) {
+    const int n4 = n >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      float4 E = reinterpret_cast<float4 *>(e)[i];
+      const float4 P = reinterpret_cast<const float4 *>(p)[i];
+      E.x = ema_one(E.x, P.x, w); E.y = ema_one(E.y, P.y, w); E.z = ema_one(E.z, P.z, w); E.w = ema_one(E.w, P.w, w);
+      reinterpret_cast<float4 *>(e)[i] = E;
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) e[i] = ema_one(e[i], p[i], w);
+  } else {
+    for (int i = threadIdx.x; i < n; i += 256) e[i] = ema_one(e[i], p[i], w);
+  }
+}
+
 inline int grid_for_vec(long long n_vec) {
   long long g = (n_vec + 255) / 256;
   if (g > 256LL * 32) g = 256LL * 32;
@@ -999,6 +1034,20 @@ int mono_grad_accumulate_f32(const void *table, int n_chunks, void *stream_) {
   const unsigned long long *ap = reinterpret_cast<const unsigned long long *>(table);
   const int *ns = reinterpret_cast<const int *>(ap + 2 * (size_t)n_chunks);
   mono::grad_accumulate_kernel<<<n_chunks, 256, 0, (hipStream_t)stream_>>>(ap, ap + n_chunks, ns);
+  return (int)hipGetLastError();
+}
+
+// e += w * (p - e) over n_chunks chunks (the weight average behind the optimizer step).  table: device buffer holding, back to back,
+// e[n_chunks], p[n_chunks] (64-bit device addresses, 4-byte aligned at least), n[n_chunks] (int32, elements per chunk).  record: NULL or the
+// guard record of this step (mono_grad_guard_f32, same stream): with its skip set nothing is stored.  n_chunks == 0: nothing to do.
+int mono_ema_update_f32(const void *table, int n_chunks, float w, const void *record, void *stream_) {
+  if (!table) return -1;
+  if (n_chunks < 0) return -2;
+  if (n_chunks == 0) return 0;
+  const unsigned long long *ep = reinterpret_cast<const unsigned long long *>(table);
+  const int *ns = reinterpret_cast<const int *>(ep + 2 * (size_t)n_chunks);
+  mono::ema_update_kernel<<<n_chunks, 256, 0, (hipStream_t)stream_>>>(ep, ep + n_chunks, ns, w,
+                                                                      reinterpret_cast<const mono::GuardRecord *>(record));
   return (int)hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 """``monosowa_amd.Detector``: camera frames in, KITTI detections out -- no KITTI directory, no DataLoader, no text files.
 
     det = Detector(cfg, checkpoint=path)            # or Detector(cfg, model=m); cfg = the YAML dict
+    det = Detector(cfg, checkpoint=path, weights="ema")     # the checkpoint's averaged weights (trainer.ema_decay)
     rows = det.detect(frames, P2, batch_size=16)    # frames: list of uint8 [h, w, 3] arrays (sizes may differ); P2: [N, 3, 4]
     for ids, rows in det.stream(batches): ...       # batches: an iterable of (frames, P2)
     det.write_kitti(rows, ids, directory)           # the files Tester.save_results writes
@@ -58,9 +59,13 @@ def check_frame(frame, index):
 
 
 class Detector:
-    def __init__(self, cfg, checkpoint=None, model=None, device=None):
+    def __init__(self, cfg, checkpoint=None, model=None, device=None, weights=None):
         if (checkpoint is None) == (model is None):
             raise ValueError("Detector needs exactly one of checkpoint= and model=")
+        if weights is not None and model is not None:
+            raise ValueError("Detector: weights= selects what is loaded from checkpoint=; it cannot be combined with model=")
+        if weights not in (None, "model", "ema"):
+            raise ValueError("Detector: weights must be 'model' or 'ema', got %r" % (weights,))
         self.cfg = cfg
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -68,7 +73,7 @@ class Detector:
         if model is None:
             from .helpers.model_helper import build_model, to_mi355x_layout
             model, _ = build_model(dict(cfg["model"], device=self.device.type))
-            load_checkpoint(model=model, optimizer=None, filename=checkpoint, map_location=self.device)
+            load_checkpoint(model=model, optimizer=None, filename=checkpoint, map_location=self.device, weights=weights or "model")
             model = model.to(self.device)
             if self.device.type == "cuda":
                 model = to_mi355x_layout(model)

@@ -62,14 +62,17 @@ class AdamW(Optimizer):
         self.skip_nonfinite = bool(skip_nonfinite)
         self._guard = None                      # pointwise.GradGuard once the device path has run
         self._guard_host = None                 # the fallback path's record
+        self._step_record = None                # device address of the guard record when THIS step's guard ran on the device
+        self._step_skipped = False              # the fallback path left THIS step out
 
     def __setstate__(self, state):
         super().__setstate__(state)
         for group in self.param_groups:
             group.setdefault("amsgrad", False)
-        for name in ("clip_max_norm", "_guard", "_guard_host"):
+        for name in ("clip_max_norm", "_guard", "_guard_host", "_step_record"):
             self.__dict__.setdefault(name, None)
         self.__dict__.setdefault("skip_nonfinite", False)
+        self.__dict__.setdefault("_step_skipped", False)
 
     @property
     def guard_enabled(self):
@@ -139,7 +142,7 @@ class AdamW(Optimizer):
                 self._guard = GradGuard(plans[0].device)
             self._guard_host = None
             self._guard.run(plans, self.clip_max_norm, self.skip_nonfinite)
-            record = self._guard.record.data_ptr()
+            record = self._step_record = self._guard.record.data_ptr()
             for plan, (group, step) in zip(plans, (w[:2] for w in work)):
                 plan.launch(group["betas"][0], group["betas"][1], group["eps"], self._step_size(group, step), record)
             return
@@ -155,6 +158,7 @@ class AdamW(Optimizer):
         host["grad_norm"], host["coef"] = norm, coef
         if self.skip_nonfinite and not bool(torch.isfinite(sumsq)):
             host["skipped_total"] += 1
+            self._step_skipped = True
             return
         for group, step, params, grads, exp_avgs, exp_avg_sqs, max_sqs in work:
             if self.clip_max_norm is not None:
@@ -172,9 +176,20 @@ class AdamW(Optimizer):
         r = self._guard.report()
         return {"grad_norm": r["grad_norm"], "coef": r["coef"], "skipped_total": r["skipped_total"]}
 
+    def guard_record_address(self):
+        """Device address of the guard record the LAST step's kernels consulted (``mono_grad_guard_f32`` ran on the device in that
+        step), else None: what a launch behind the step -- the weight average -- hands to its kernel so that it skips with the step."""
+        return self._step_record
+
+    def last_step_skipped(self):
+        """True when the guard's host fallback left the LAST step out.  A skip decided on the device is not known here (False): there
+        ``guard_record_address()`` is what follows it."""
+        return self._step_skipped
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
+        self._step_record, self._step_skipped = None, False
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()

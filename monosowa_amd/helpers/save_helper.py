@@ -1,6 +1,8 @@
 """Checkpoint dictionary {'epoch','model_state','optimizer_state','best_result','best_epoch'} saved
 as '<name>.pth' (reference: lib/helpers/save_helper.py:6-45).  DataParallel / DDP wrappers are
-unwrapped on save so checkpoints are interchangeable with the reference's."""
+unwrapped on save so checkpoints are interchangeable with the reference's.  With a weight average (monosowa_amd/ema.py,
+``trainer.ema_decay``) a sixth key, 'ema_state' = ``ModelEMA.state_dict()``, rides along; without one the dictionary is the reference's."""
+import logging
 import os
 
 import torch
@@ -18,7 +20,7 @@ def model_state_to_cpu(model_state):
     return out
 
 
-def get_checkpoint_state(model=None, optimizer=None, epoch=None, best_result=None, best_epoch=None):
+def get_checkpoint_state(model=None, optimizer=None, epoch=None, best_result=None, best_epoch=None, ema=None):
     optim_state = optimizer.state_dict() if optimizer is not None else None
     if model is None:
         model_state = None
@@ -26,15 +28,26 @@ def get_checkpoint_state(model=None, optimizer=None, epoch=None, best_result=Non
         model_state = model_state_to_cpu(unwrap(model).state_dict())
     else:
         model_state = model.state_dict()
-    return {"epoch": epoch, "model_state": model_state, "optimizer_state": optim_state,
-            "best_result": best_result, "best_epoch": best_epoch}
+    state = {"epoch": epoch, "model_state": model_state, "optimizer_state": optim_state,
+             "best_result": best_result, "best_epoch": best_epoch}
+    if ema is not None:
+        ema_state = ema.state_dict()
+        if model is not None and unwrap(model) is not model:
+            ema_state["module"] = model_state_to_cpu(ema_state["module"])
+        state["ema_state"] = ema_state
+    return state
 
 
 def save_checkpoint(state, filename):
     torch.save(state, "{}.pth".format(filename))
 
 
-def load_checkpoint(model, optimizer, filename, map_location, logger=None):
+def load_checkpoint(model, optimizer, filename, map_location, logger=None, ema=None, weights="model"):
+    """``weights="ema"``: ``model`` receives the checkpoint's averaged weights (``ema_state["module"]``) instead of ``model_state``;
+    KeyError when the file has none.  ``ema`` (a ``ModelEMA`` over ``model``): restored from ``ema_state``; from a checkpoint
+    without one it starts over from the loaded weights (``updates = 0``), with one warning."""
+    if weights not in ("model", "ema"):
+        raise ValueError("load_checkpoint: weights must be 'model' or 'ema', got %r" % (weights,))
     if not os.path.isfile(filename):
         raise FileNotFoundError(filename)
     if logger is not None:
@@ -43,8 +56,20 @@ def load_checkpoint(model, optimizer, filename, map_location, logger=None):
     epoch = checkpoint.get("epoch", -1)
     best_result = checkpoint.get("best_result", 0.0)
     best_epoch = checkpoint.get("best_epoch", 0.0)
-    if model is not None and checkpoint["model_state"] is not None:
+    if weights == "ema":
+        if checkpoint.get("ema_state") is None:
+            raise KeyError("checkpoint '%s' has no 'ema_state': it was written without trainer.ema_decay" % filename)
+        if model is not None:
+            unwrap(model).load_state_dict(checkpoint["ema_state"]["module"])
+    elif model is not None and checkpoint["model_state"] is not None:
         unwrap(model).load_state_dict(checkpoint["model_state"])
+    if ema is not None:
+        if checkpoint.get("ema_state") is not None:
+            ema.load_state_dict(checkpoint["ema_state"])
+        else:
+            ema.reset()
+            (logger or logging.getLogger(__name__)).warning(
+                "checkpoint '%s' has no 'ema_state': the weight average starts from the loaded weights with updates = 0", filename)
     if optimizer is not None and checkpoint["optimizer_state"] is not None:
         optimizer.load_state_dict(checkpoint["optimizer_state"])
     if logger is not None:

@@ -58,19 +58,25 @@ class Tester(object):
         self.train_cfg = train_cfg
         self.model_name = model_name
         self.last_img_per_s = None
+        # tester.weights: 'model' (default) | 'ema' -- which weights test() takes from the checkpoint files (save_helper.load_checkpoint)
+        self.weights = cfg.get("weights", "model")
+        if self.weights not in ("model", "ema"):
+            raise ValueError("tester.weights must be 'model' or 'ema', got %r" % (self.weights,))
 
     def test(self):
         assert self.cfg["mode"] in ["single", "all"]
         if self.cfg["mode"] == "single":
             path = os.path.join(self.output_dir, "checkpoint_epoch_{}.pth".format(self.cfg["checkpoint"]))
-            load_checkpoint(model=self.model, optimizer=None, filename=path, map_location=self.device, logger=self.logger)
+            load_checkpoint(model=self.model, optimizer=None, filename=path, map_location=self.device, logger=self.logger,
+                            weights=self.weights)
             self.model.to(self.device)
             self.inference()
             return self.evaluate()
         ckpts = sorted(glob.glob(os.path.join(self.output_dir, "checkpoint_epoch_*.pth")), key=os.path.getmtime)
         result = None
         for path in ckpts:
-            load_checkpoint(model=self.model, optimizer=None, filename=path, map_location=self.device, logger=self.logger)
+            load_checkpoint(model=self.model, optimizer=None, filename=path, map_location=self.device, logger=self.logger,
+                            weights=self.weights)
             self.model.to(self.device)
             self.inference()
             result = self.evaluate()

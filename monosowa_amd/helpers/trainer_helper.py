@@ -12,6 +12,11 @@ checkpoint naming.  Differences that do not change results:
 * ``trainer.global_batch: N`` (optional, absent from the shipped config): N images per optimizer step whatever the number of
   GPUs, by gradient accumulation over K = N / (world size * per-GPU batch) loader batches -- one *cycle*.  A cycle is, by
   definition, one DDP step of K * W ranks: see ``Trainer.train_cycle``.  Absent, 0 or K = 1: the loop below is the plain one.
+* ``trainer.ema_decay: X`` (optional, absent from the shipped config; ``trainer.ema_warmup``, default true): an exponential moving
+  average of the weights (monosowa_amd/ema.py), updated once per optimizer step right behind it.  The evaluation after an epoch then
+  runs on the averaged weights, so ``checkpoint_best`` follows them, and every checkpoint carries an ``ema_state`` beside
+  ``model_state``.  Absent, None or 0: nothing is built, allocated, launched or saved.  Under DDP every rank keeps its own copy
+  (parameters are bitwise equal across ranks after the all-reduce, so the copies are); rank 0 saves; no collective is added.
 """
 import contextlib
 import os
@@ -105,17 +110,25 @@ class Trainer(object):
         self._guard_skipped = 0          # optimizer.guard_report()["skipped_total"] at the end of the previous epoch
         self.accum_steps = self._accum_steps(cfg.get("global_batch"), train_loader)      # K: loader batches per optimizer step
         self._accumulator = None
+        ema_decay = self._ema_decay(cfg.get("ema_decay"))
+        self.ema = None                  # ModelEMA with trainer.ema_decay, built below once the weights are the ones training starts from
 
         if cfg.get("pretrain_model"):
             assert os.path.exists(cfg["pretrain_model"])
             load_checkpoint(model=self.model, optimizer=None, filename=cfg["pretrain_model"],
                             map_location=self.device, logger=self.logger)
-        if cfg.get("resume_model", None):
-            resume = os.path.join(self.output_dir, "checkpoint.pth")
+        resume = os.path.join(self.output_dir, "checkpoint.pth") if cfg.get("resume_model", None) else None
+        if resume is not None:
             assert os.path.exists(resume)
+            self.model.to(self.device)
+        if ema_decay is not None:
+            # after the layout change and the moves above: every averaged tensor has its parameter's strides and device
+            from ..ema import ModelEMA
+            self.ema = ModelEMA(self.model, ema_decay, warmup=bool(cfg.get("ema_warmup", True)))
+        if resume is not None:
             self.epoch, self.best_result, self.best_epoch = load_checkpoint(
-                model=self.model.to(self.device), optimizer=self.optimizer, filename=resume,
-                map_location=self.device, logger=self.logger)
+                model=self.model, optimizer=self.optimizer, filename=resume,
+                map_location=self.device, logger=self.logger, ema=self.ema)
             self.lr_scheduler.last_epoch = self.epoch - 1
             self.logger.info("Loading Checkpoint... Best Result:{}, Best Epoch:{}".format(self.best_result, self.best_epoch))
 
@@ -138,16 +151,13 @@ class Trainer(object):
             if (self.epoch % self.cfg["save_frequency"]) == 0 and main:
                 os.makedirs(self.output_dir, exist_ok=True)
                 name = "checkpoint_epoch_%d" % self.epoch if self.cfg["save_all"] else "checkpoint"
-                save_checkpoint(get_checkpoint_state(self.model, self.optimizer, self.epoch, best_result, best_epoch),
-                                os.path.join(self.output_dir, name))
+                save_checkpoint(self._checkpoint_state(best_result, best_epoch), os.path.join(self.output_dir, name))
                 if self.tester is not None:
-                    self.logger.info("Test Epoch {}".format(self.epoch))
-                    self.tester.inference()
-                    cur = self.tester.evaluate()
+                    self.logger.info("Test Epoch {}".format(self.epoch) + (" (EMA weights)" if self.ema is not None else ""))
+                    cur = self._evaluate()
                     if cur > best_result:
                         best_result, best_epoch = cur, self.epoch
-                        save_checkpoint(get_checkpoint_state(self.model, self.optimizer, self.epoch, best_result, best_epoch),
-                                        os.path.join(self.output_dir, "checkpoint_best"))
+                        save_checkpoint(self._checkpoint_state(best_result, best_epoch), os.path.join(self.output_dir, "checkpoint_best"))
                     self.logger.info("Best Result:{}, epoch:{}".format(best_result, best_epoch))
             if (self.epoch % self.cfg["save_frequency"]) == 0 and misc.is_dist_avail_and_initialized():
                 # rank 0 saved / evaluated alone: the other ranks wait here instead of inside the next epoch's first
@@ -158,6 +168,34 @@ class Trainer(object):
             bar.update()
         self.logger.info("Best Result:{}, epoch:{}".format(best_result, best_epoch))
         return None
+
+    def _checkpoint_state(self, best_result, best_epoch):
+        if self.ema is None:
+            return get_checkpoint_state(self.model, self.optimizer, self.epoch, best_result, best_epoch)
+        return get_checkpoint_state(self.model, self.optimizer, self.epoch, best_result, best_epoch, ema=self.ema)
+
+    def _evaluate(self):
+        """The tester's pass after an epoch; with the weight average on, over the averaged weights: the tester's model is swapped for
+        the pass and put back afterwards, whatever happens."""
+        if self.ema is None:
+            self.tester.inference()
+            return self.tester.evaluate()
+        live = self.tester.model
+        self.tester.model = self.ema.sync_untracked()
+        try:
+            self.tester.inference()
+            return self.tester.evaluate()
+        finally:
+            self.tester.model = live
+
+    @staticmethod
+    def _ema_decay(value):
+        """``trainer.ema_decay``: None for absent, None or 0 (off), else the decay, a number inside (0, 1)."""
+        if value is None or (not isinstance(value, bool) and isinstance(value, (int, float)) and value == 0):
+            return None
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 < float(value) < 1.0:
+            raise ValueError("trainer.ema_decay = %r is not a number inside (0, 1) (absent, None or 0: off)" % (value,))
+        return float(value)
 
     def train_step(self, inputs, calibs, targets, info=None):
         """One optimizer step on a device-resident batch; returns (total loss tensor, loss dict)."""
@@ -170,6 +208,8 @@ class Trainer(object):
         total = weighted_total(loss_dict, weight_dict)
         total.backward()
         self.optimizer.step()
+        if self.ema is not None:
+            self.ema.update(self.optimizer)
         return total, loss_dict
 
     @staticmethod
@@ -240,6 +280,8 @@ class Trainer(object):
             acc.collect(k)
         acc.install()
         self.optimizer.step()
+        if self.ema is not None:
+            self.ema.update(self.optimizer)
         return total, loss_dict
 
     def train_one_epoch(self, epoch):

@@ -15,7 +15,7 @@ SYMBOLS = ("mono_bias_act_f32", "mono_bias_relu_maxpool_nhwc_f32", "mono_conv1x1
            "mono_relu_dropout_bwd_f32", "mono_matched_losses_fwd_f32", "mono_matched_losses_bwd_f32", "mono_ddn_loss_blocks",
            "mono_ddn_loss_fwd_f32", "mono_ddn_loss_bwd_f32", "mono_depth_expect_fwd_f32", "mono_depth_expect_bwd_f32", "mono_focal_fwd_f32", "mono_focal_bwd_f32", "mono_head_tail_fwd_f32", "mono_head_tail_bwd_f32", "mono_match_cost_f32", "mono_refine_reference_f32", "mono_relu_dropout_bwd_colsum_f32", "mono_sum_slices_f32", "mono_colsum_any_blocks", "mono_colsum_any_f32", "mono_relu_grad_mask3_f32", "mono_lsap_match_flat_f32",
            "mono_linear_wgrad_workspace", "mono_linear_wgrad_f32", "mono_colsum_levels_blocks", "mono_colsum_levels_f32", "mono_relu_grad_scale_f32",
-           "mono_set_deterministic", "mono_groupnorm_stats_doubles", "mono_groupnorm_part_doubles", "mono_grad_accumulate_f32")
+           "mono_set_deterministic", "mono_groupnorm_stats_doubles", "mono_groupnorm_part_doubles", "mono_grad_accumulate_f32", "mono_ema_update_f32")
 _lib = None
 
 
@@ -98,6 +98,8 @@ def load():
         lib.mono_grad_guard_f32.argtypes = [P, P, I, ctypes.c_float, I, P, P, P]
         lib.mono_grad_accumulate_f32.restype = I
         lib.mono_grad_accumulate_f32.argtypes = [P, I, P]
+        lib.mono_ema_update_f32.restype = I
+        lib.mono_ema_update_f32.argtypes = [P, I, ctypes.c_float, P, P]
         lib.mono_colsum_strided_f32.restype = I
         lib.mono_colsum_strided_f32.argtypes = [P, P, P, I, LL, LL, I, P]
         lib.mono_colsum_levels_blocks.restype = I
