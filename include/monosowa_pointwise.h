@@ -142,6 +142,27 @@ int mono_grad_accumulate_f32(const void *table, int n_chunks, void *stream);
  * Returns -1 for a NULL table, -2 for n_chunks < 0; n_chunks == 0 launches nothing and returns 0. */
 int mono_ema_update_f32(const void *table, int n_chunks, float w, const void *record, void *stream);
 
+/* Per-step training record (monosowa_amd/history.py), taken behind the optimizer step from the chunk tables its AdamW launches have just
+ * used: per module group q the three doubles
+ *     out[3 q]     grad_sumsq      sum of (double)g * (double)g over the gradient elements of the group's chunks
+ *     out[3 q + 1] param_sumsq     the same over the parameter elements (after the step; the untouched ones when the guard skipped it)
+ *     out[3 q + 2] grad_nonfinite  number of gradient elements that are NaN or +-Inf
+ * and, behind the groups, out[3 n_groups + {0, 1, 2}] = norm, coef, skip of the guard record, widened to double.
+ * tables / n_chunks: HOST arrays of n_tables (1..8) device chunk tables in mono_adamw_step_f32's layout and their chunk counts (>= 0); only
+ * the p, g and n columns are read.  groups: HOST array of n_tables device int32[n_chunks[t]] arrays, the group id of every chunk
+ * (0 <= id < n_groups, 1 <= n_groups <= 64; a chunk with any other id is counted nowhere).  partials: device scratch of
+ * 3 * sum(n_chunks) doubles.  record: NULL (the last three outputs are not written), or the guard record mono_grad_guard_f32 wrote earlier
+ * on the same stream.
+ * Two launches, as in mono_grad_guard_f32: one workgroup per chunk writes its three f64 partials (exact products, so neither 1e25- nor
+ * 1e-30-sized values overflow or vanish; NaN and +-Inf enter the sums as IEEE f64 takes them), then one workgroup per group adds the
+ * partials of its chunks in a fixed order (table index, then chunk index).  No atomics: the same inputs give the same bits, wherever out
+ * lies.  A group without chunks gets exact zeros.  float4 loads where both addresses of a chunk are 16-byte aligned, scalar loads
+ * otherwise (4-byte alignment at least) and for tails.  Nothing but partials and out is written.
+ * Returns -1 for a NULL pointer among tables, n_chunks, groups, partials, out (or a NULL table / group array with chunks), -2 for n_tables
+ * outside 1..8, n_groups outside 1..64 or a negative chunk count; a total of 0 chunks launches nothing and returns 0. */
+int mono_step_stats_f32(const void *const *tables, const int *n_chunks, const int *const *groups, int n_tables, int n_groups,
+                        const void *record, double *partials, double *out, void *stream);
+
 /* dW[M, N] = dY[R, M]^T . X[R, N] and (db != NULL) db[M] = the column sums of dY, f32, exact products (v_mfma_f32_32x32x2_f32), summed in a
  * fixed order (no atomics): the weight and bias gradients of y = x W^T + b over a few thousand tokens -- autograd's AddmmBackward of the
  * nn.Linear layers of the decoder / depth-token encoder (reference depthaware_transformer.py:339-354,440-515) -- in two launches that

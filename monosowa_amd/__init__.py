@@ -7,4 +7,7 @@ def __getattr__(name):
     if name == "Detector":                  # the public inference API (monosowa_amd/detector.py); imported on first use
         from .detector import Detector
         return Detector
+    if name == "StepHistory":               # the per-step training record (monosowa_amd/history.py)
+        from .history import StepHistory
+        return StepHistory
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -736,6 +736,107 @@ __global__ __launch_bounds__(256) void ema_update_kernel(const unsigned long lon
   }
 }
 
+// ---- per-step training record: per module group, sum of g^2, sum of p^2 and the number of non-finite gradient elements --------------------
+// The chunk tables adamw_kernel reads (p, g and n columns; up to STATS_MAX_TABLES of them, first[] as in GuardGroups) plus, per table, the
+// module-group id of every chunk.  Chunks are numbered over all tables in table order: that number indexes `partials`.
+constexpr int STATS_MAX_TABLES = 8;
+constexpr int STATS_MAX_GROUPS = 64;
+struct StatsTables {
+  const unsigned long long *p[STATS_MAX_TABLES];
+  const unsigned long long *g[STATS_MAX_TABLES];
+  const int *n[STATS_MAX_TABLES];
+  const int *group[STATS_MAX_TABLES];
+  int first[STATS_MAX_TABLES + 1];
+  int count;
+};
+
+// Three such sums of one workgroup (guard_block_sum's order for each), on every thread.
+__device__ __forceinline__ void stats_block_sum3(double &a, double &b, double &c, double (*red)[4]) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_xor(a, off, 64);
+    b += __shfl_xor(b, off, 64);
+    c += __shfl_xor(c, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; red[2][threadIdx.x >> 6] = c;
+  }
+  __syncthreads();
+  a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+  b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+  c = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
+}
+
+// One workgroup per chunk: partials[3 * chunk + {0, 1, 2}] = sum of (double)g * (double)g, sum of (double)p * (double)p, number of g that
+// are NaN or +-Inf (exponent field all ones; a count below 2^15 per chunk, exact as a double).  The products are exact in f64, as in
+// grad_guard_partial_kernel; non-finite values enter the sums as IEEE f64 takes them.  float4 loads when both addresses are 16-byte
+// aligned, scalar loads otherwise and for the tail.  Both inputs are read only.
+__global__ __launch_bounds__(256) void step_stats_partial_kernel(StatsTables t, double *__restrict__ partials) {
+  const int c = blockIdx.x;
+  int k = 0;
+#pragma unroll
+  for (int j = 1; j < STATS_MAX_TABLES; ++j)
+    if (j < t.count && c >= t.first[j]) k = j;
+  const int local = c - t.first[k];
+  const unsigned long long pa = t.p[k][local], ga = t.g[k][local];
+  const float *p = reinterpret_cast<const float *>(pa);
+  const float *g = reinterpret_cast<const float *>(ga);
+  const int n = t.n[k][local];
+  double gs = 0.0, ps = 0.0;
+  int bad = 0;
+  auto add = [&gs, &ps, &bad](float gv, float pv) {
+    const double gd = (double)gv, pd = (double)pv;
+    gs = fma(gd, gd, gs);
+    ps = fma(pd, pd, ps);
+    bad += (__float_as_uint(gv) & 0x7f800000u) == 0x7f800000u ? 1 : 0;
+  };
+  if (((pa | ga) & 15ull) == 0) {
+    const int n4 = n >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      const float4 G = reinterpret_cast<const float4 *>(g)[i];
+      const float4 P = reinterpret_cast<const float4 *>(p)[i];
+      add(G.x, P.x); add(G.y, P.y); add(G.z, P.z); add(G.w, P.w);
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) add(g[i], p[i]);
+  } else {
+    for (int i = threadIdx.x; i < n; i += 256) add(g[i], p[i]);
+  }
+  __shared__ double red[3][4];
+  double cnt = (double)bad;
+  stats_block_sum3(gs, ps, cnt, red);
+  if (threadIdx.x == 0) {
+    partials[3 * (size_t)c] = gs; partials[3 * (size_t)c + 1] = ps; partials[3 * (size_t)c + 2] = cnt;
+  }
+}
+
+// Workgroup q adds the partials of the chunks of group q: thread t takes chunks t, t + 256, ... of the numbering above (table index, then
+// chunk index) and skips those of other groups, the 256 sums are added in guard_block_sum's order.  out[3 * q + {0, 1, 2}]; a group without
+// chunks gets exact zeros.  Workgroup 0 also copies norm, coef and skip of the guard record (when there is one), widened to double, to
+// out[3 * n_groups + {0, 1, 2}].
+__global__ __launch_bounds__(256) void step_stats_fold_kernel(StatsTables t, const double *__restrict__ partials, int n_groups,
+                                                              const GuardRecord *__restrict__ rec, double *__restrict__ out) {
+  const int q = blockIdx.x;
+  const int total = t.first[STATS_MAX_TABLES];
+  double gs = 0.0, ps = 0.0, cnt = 0.0;
+  for (int c = threadIdx.x; c < total; c += 256) {
+    int k = 0;
+#pragma unroll
+    for (int j = 1; j < STATS_MAX_TABLES; ++j)
+      if (j < t.count && c >= t.first[j]) k = j;
+    if (t.group[k][c - t.first[k]] == q) {
+      gs += partials[3 * (size_t)c]; ps += partials[3 * (size_t)c + 1]; cnt += partials[3 * (size_t)c + 2];
+    }
+  }
+  __shared__ double red[3][4];
+  stats_block_sum3(gs, ps, cnt, red);
+  if (threadIdx.x == 0) {
+    out[3 * q] = gs; out[3 * q + 1] = ps; out[3 * q + 2] = cnt;
+    if (q == 0 && rec != nullptr) {
+      out[3 * n_groups] = (double)rec->norm; out[3 * n_groups + 1] = (double)rec->coef; out[3 * n_groups + 2] = (double)rec->skip;
+    }
+  }
+}
+
 inline int grid_for_vec(long long n_vec) {
   long long g = (n_vec + 255) / 256;
   if (g > 256LL * 32) g = 256LL * 32;
@@ -1078,6 +1179,40 @@ int mono_grad_guard_f32(const void *const *tables, const int *n_chunks, int n_gr
   mono::grad_guard_partial_kernel<<<(int)total, 256, 0, st>>>(t, partials);
   mono::grad_guard_fold_kernel<<<1, 256, 0, st>>>(partials, (int)total, max_norm, skip_nonfinite,
                                                  reinterpret_cast<mono::GuardRecord *>(record));
+  return (int)hipGetLastError();
+}
+
+// Per module group: sum of g^2, sum of p^2 (both as exact f64 products) and the number of non-finite gradient elements, over the chunk
+// tables of this step's AdamW launches (the layout of mono_adamw_step_f32; the p, g and n columns are read), in two launches, fixed
+// summation order, no atomics: the same inputs give the same bits wherever `out` lies.  tables / n_chunks / groups: HOST arrays of n_tables
+// (1..8) device tables, their chunk counts (0 allowed) and device int32[n_chunks[t]] arrays holding the group id (0 <= id < n_groups; any
+// other id is counted nowhere) of every chunk.  partials: device scratch of 3 * sum(n_chunks) doubles.  out: 3 * n_groups + 3 doubles,
+// {grad_sumsq, param_sumsq, grad_nonfinite} per group, then norm, coef, skip of `record` (NULL: those three are not written).  Nothing but
+// partials and out is written.  Zero chunks in all: nothing is launched, out keeps what the caller put there.
+int mono_step_stats_f32(const void *const *tables, const int *n_chunks, const int *const *groups, int n_tables, int n_groups,
+                        const void *record, double *partials, double *out, void *stream_) {
+  if (!tables || !n_chunks || !groups || !partials || !out) return -1;
+  if (n_tables <= 0 || n_tables > mono::STATS_MAX_TABLES || n_groups <= 0 || n_groups > mono::STATS_MAX_GROUPS) return -2;
+  mono::StatsTables t = {};
+  long long total = 0;
+  for (int k = 0; k < n_tables; ++k) {
+    if (n_chunks[k] < 0) return -2;
+    if (n_chunks[k] > 0 && (!tables[k] || !groups[k])) return -1;
+    const unsigned long long *pp = reinterpret_cast<const unsigned long long *>(tables[k]);
+    t.p[k] = pp;
+    t.g[k] = pp + n_chunks[k];
+    t.n[k] = reinterpret_cast<const int *>(pp + 4 * (size_t)n_chunks[k]);
+    t.group[k] = groups[k];
+    t.first[k] = (int)total;
+    total += n_chunks[k];
+    if (total > 0x7fffffffLL / 3) return -2;
+  }
+  for (int k = n_tables; k <= mono::STATS_MAX_TABLES; ++k) t.first[k] = (int)total;
+  t.count = n_tables;
+  if (total == 0) return 0;
+  hipStream_t st = (hipStream_t)stream_;
+  mono::step_stats_partial_kernel<<<(int)total, 256, 0, st>>>(t, partials);
+  mono::step_stats_fold_kernel<<<n_groups, 256, 0, st>>>(t, partials, n_groups, reinterpret_cast<const mono::GuardRecord *>(record), out);
   return (int)hipGetLastError();
 }
 

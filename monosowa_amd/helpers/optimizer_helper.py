@@ -64,12 +64,13 @@ class AdamW(Optimizer):
         self._guard_host = None                 # the fallback path's record
         self._step_record = None                # device address of the guard record when THIS step's guard ran on the device
         self._step_skipped = False              # the fallback path left THIS step out
+        self._step_plans = None                 # the FusedAdamWPlans THIS step launched, in launch order; None: some bucket went through foreach
 
     def __setstate__(self, state):
         super().__setstate__(state)
         for group in self.param_groups:
             group.setdefault("amsgrad", False)
-        for name in ("clip_max_norm", "_guard", "_guard_host", "_step_record"):
+        for name in ("clip_max_norm", "_guard", "_guard_host", "_step_record", "_step_plans"):
             self.__dict__.setdefault(name, None)
         self.__dict__.setdefault("skip_nonfinite", False)
         self.__dict__.setdefault("_step_skipped", False)
@@ -109,9 +110,12 @@ class AdamW(Optimizer):
             return False
         beta1, beta2 = group["betas"]
         plan.step(grads, beta1, beta2, group["eps"], self._step_size(group, step))
+        if self._step_plans is not None:
+            self._step_plans.append(plan)
         return True
 
     def _foreach_step(self, group, step, params, grads, exp_avgs, exp_avg_sqs, max_sqs):
+        self._step_plans = None
         beta1, beta2 = group["betas"]
         torch._foreach_mul_(exp_avgs, beta1)
         torch._foreach_add_(exp_avgs, grads, alpha=1 - beta1)
@@ -145,7 +149,9 @@ class AdamW(Optimizer):
             record = self._step_record = self._guard.record.data_ptr()
             for plan, (group, step) in zip(plans, (w[:2] for w in work)):
                 plan.launch(group["betas"][0], group["betas"][1], group["eps"], self._step_size(group, step), record)
+            self._step_plans = plans
             return
+        self._step_plans = None                            # a skipped step launches nothing at all: not a fused one either
         grads = [g for w in work for g in w[3]]
         sumsq = torch.stack([g.detach().double().pow(2).sum().to(grads[0].device) for g in grads]).sum()
         norm = sumsq.sqrt().float()
@@ -181,6 +187,13 @@ class AdamW(Optimizer):
         step), else None: what a launch behind the step -- the weight average -- hands to its kernel so that it skips with the step."""
         return self._step_record
 
+    def last_fused_plans(self):
+        """The ``FusedAdamWPlan``s the LAST step launched, in launch order, their tables refreshed for that step's gradients -- what a
+        launch behind the step reads the step's parameter, gradient and count columns from.  None when any bucket of that step took
+        the foreach path (CPU tensors, ``amsgrad``, non-dense layouts) or no step has run; an empty list when no parameter had a
+        gradient."""
+        return None if self._step_plans is None else list(self._step_plans)
+
     def last_step_skipped(self):
         """True when the guard's host fallback left the LAST step out.  A skip decided on the device is not known here (False): there
         ``guard_record_address()`` is what follows it."""
@@ -189,7 +202,7 @@ class AdamW(Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
-        self._step_record, self._step_skipped = None, False
+        self._step_record, self._step_skipped, self._step_plans = None, False, []
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()

@@ -17,8 +17,17 @@ checkpoint naming.  Differences that do not change results:
   runs on the averaged weights, so ``checkpoint_best`` follows them, and every checkpoint carries an ``ema_state`` beside
   ``model_state``.  Absent, None or 0: nothing is built, allocated, launched or saved.  Under DDP every rank keeps its own copy
   (parameters are bitwise equal across ranks after the all-reduce, so the copies are); rank 0 saves; no collective is added.
+* ``trainer.history: true`` (optional, absent from the shipped config): a per-step record kept on the device (monosowa_amd/history.py) --
+  every loss term, per module group the gradient norm, the parameter norm and the number of non-finite gradient elements, the guard's
+  verdict -- without a synchronisation in the step.  It is read once per epoch, behind the guard check: every rank drains (under DDP
+  the loss columns are averaged over the ranks by ONE all-reduce of the ring; the norm columns are equal across ranks), rank 0 appends
+  one JSON object per step to ``<output_dir>/history.jsonl`` (truncated when a run starts without ``resume_model``, appended to with
+  it; non-finite numbers as the strings "nan", "inf", "-inf") and logs the epoch means of the weighted loss terms, the median and
+  maximum of the global gradient norm and one line per step that had non-finite gradients.  Absent, None or false: nothing is built,
+  allocated, launched, written or logged; nothing is added to a checkpoint either way.
 """
 import contextlib
+import math
 import os
 
 import numpy as np
@@ -112,6 +121,10 @@ class Trainer(object):
         self._accumulator = None
         ema_decay = self._ema_decay(cfg.get("ema_decay"))
         self.ema = None                  # ModelEMA with trainer.ema_decay, built below once the weights are the ones training starts from
+        history = self._history_flag(cfg.get("history"))
+        self.history = None              # StepHistory with trainer.history, built below once the model is where it trains
+        self._history_step = 0           # optimizer steps committed in the current epoch
+        self._history_fresh = not cfg.get("resume_model", None)      # the first write of this run truncates history.jsonl
 
         if cfg.get("pretrain_model"):
             assert os.path.exists(cfg["pretrain_model"])
@@ -125,6 +138,10 @@ class Trainer(object):
             # after the layout change and the moves above: every averaged tensor has its parameter's strides and device
             from ..ema import ModelEMA
             self.ema = ModelEMA(self.model, ema_decay, warmup=bool(cfg.get("ema_warmup", True)))
+        if history:
+            from ..history import StepHistory
+            steps = -(-len(train_loader) // self.accum_steps)          # optimizer steps of an epoch: never a drain inside one
+            self.history = StepHistory(self.model, self.detr_loss.weight_dict, max(steps, 1))
         if resume is not None:
             self.epoch, self.best_result, self.best_epoch = load_checkpoint(
                 model=self.model, optimizer=self.optimizer, filename=resume,
@@ -136,6 +153,8 @@ class Trainer(object):
         start_epoch = self.epoch
         best_result, best_epoch = self.best_result, self.best_epoch
         main = misc.is_main_process()
+        if self.history is not None and main:
+            self._history_file()                           # a run without resume_model starts from an empty file
         bar = tqdm.tqdm(range(start_epoch, self.cfg["max_epoch"]), dynamic_ncols=True, leave=True, desc="epochs", disable=not main)
         for epoch in range(start_epoch, self.cfg["max_epoch"]):
             np.random.seed(np.random.get_state()[1][0] + epoch)
@@ -197,6 +216,62 @@ class Trainer(object):
             raise ValueError("trainer.ema_decay = %r is not a number inside (0, 1) (absent, None or 0: off)" % (value,))
         return float(value)
 
+    @staticmethod
+    def _history_flag(value):
+        """``trainer.history``: False for absent, None or false, True for true; anything else is refused."""
+        if value is None:
+            return False
+        if not isinstance(value, bool):
+            raise ValueError("trainer.history = %r is not a bool (absent, None or false: off)" % (value,))
+        return value
+
+    def _history_commit(self, micro_batches):
+        self.history.commit(self.optimizer, epoch=self.epoch, step=self._history_step, lr=self.optimizer.param_groups[0]["lr"],
+                            micro_batches=micro_batches)
+        self._history_step += 1
+
+    def _history_file(self):
+        """Path of ``history.jsonl``; the first call of a run without ``resume_model`` leaves the file empty."""
+        path = os.path.join(self.output_dir, "history.jsonl")
+        if self._history_fresh:
+            os.makedirs(self.output_dir, exist_ok=True)
+            open(path, "w").close()
+            self._history_fresh = False
+        return path
+
+    def _drain_history(self, epoch):
+        """End of an epoch with ``trainer.history``: the ring to the host (the one synchronisation of the record; every rank takes
+        part in the all-reduce of the loss columns), rank 0 appends to ``history.jsonl`` and logs the epoch's summary."""
+        from ..history import to_json
+        rows = self.history.drain()
+        self._history_step = 0
+        if not misc.is_main_process():
+            return
+        path = self._history_file()
+        os.makedirs(self.output_dir, exist_ok=True)
+        with open(path, "a") as f:
+            for row in rows:
+                f.write(to_json(row) + "\n")
+        weight_dict = self.detr_loss.weight_dict
+        finite = [r for r in rows if math.isfinite(r["loss_detr"])]
+        if finite:
+            means = {k: float(np.mean([r["losses"][k] for r in finite])) * float(weight_dict[k]) for k in finite[0]["losses"]}
+            self.logger.info("Epoch {}: mean over {} of {} steps: loss_detr: {:.4f}, ".format(
+                epoch, len(finite), len(rows), float(np.mean([r["loss_detr"] for r in finite])))
+                + ", ".join("%s: %.4f" % kv for kv in means.items()))
+        else:
+            self.logger.info("Epoch {}: mean over 0 of {} steps: no step with a finite loss_detr".format(epoch, len(rows)))
+        if rows:
+            with np.errstate(invalid="ignore", over="ignore"):
+                norms = [float(np.sqrt(np.sum(np.square(list(r["grad_norm"].values()))))) for r in rows]
+            self.logger.info("Epoch {}: grad_norm median: {:.4g}, max: {:.4g}".format(epoch, float(np.median(norms)), float(np.max(norms))))
+        for r in rows:
+            bad = {g: n for g, n in r["grad_nonfinite"].items() if n > 0}
+            if bad:
+                skipped = "skipped" if r.get("guard", {}).get("skip") else "not skipped"
+                self.logger.info("Epoch {} step {}: non-finite gradients ({}): {}".format(
+                    epoch, r["step"], skipped, ", ".join("%s: %d" % kv for kv in bad.items())))
+
     def train_step(self, inputs, calibs, targets, info=None):
         """One optimizer step on a device-resident batch; returns (total loss tensor, loss dict)."""
         img_sizes = targets["img_size"]
@@ -207,7 +282,11 @@ class Trainer(object):
         weight_dict = self.detr_loss.weight_dict
         total = weighted_total(loss_dict, weight_dict)
         total.backward()
+        if self.history is not None:
+            self.history.add_losses(loss_dict, total)
         self.optimizer.step()
+        if self.history is not None:
+            self._history_commit(1)
         if self.ema is not None:
             self.ema.update(self.optimizer)
         return total, loss_dict
@@ -255,7 +334,9 @@ class Trainer(object):
         forward (its own matching and size compensation) and is normalised by the box count of the whole cycle over all ranks,
         max(n * group_num / (K * W), 1); its weighted loss enters with 1 / K, which is DDP's gradient mean.  The gradients add up in
         micro-batch order, one float32 add per element and micro-step; the optimizer (and its guard) sees the sum once.  Under DDP
-        only the last backward all-reduces.  The staged copy of a batch lives for its own micro-step only."""
+        only the last backward all-reduces.  The staged copy of a batch lives for its own micro-step only.  With ``trainer.history`` the
+        row of the cycle holds sum_k term_k / K for every raw loss term (``add_losses`` with scale 1 / K) and sum_k total_k for
+        ``loss_detr``: ``total`` carries its 1 / K already and is added as it is."""
         K = len(raws)
         if K == 1:                                         # the tail of an epoch: exactly a plain step
             return self.train_step(*stage_batch(raws[0], self.device))
@@ -277,9 +358,13 @@ class Trainer(object):
                 loss_dict = self.detr_loss(outputs, target_list, None, info, num_boxes=num_boxes)
                 total = weighted_total(loss_dict, weight_dict) / K
                 total.backward()
+            if self.history is not None:
+                self.history.add_losses(loss_dict, total, scale=1.0 / K)
             acc.collect(k)
         acc.install()
         self.optimizer.step()
+        if self.history is not None:
+            self._history_commit(K)
         if self.ema is not None:
             self.ema.update(self.optimizer)
         return total, loss_dict
@@ -324,7 +409,11 @@ class Trainer(object):
         matcher = getattr(self.detr_loss, "matcher", None)
         if matcher is not None and hasattr(matcher, "check_device_status"):
             matcher.check_device_status(block=True)
-        self._check_guard(epoch, steps)
+        try:
+            self._check_guard(epoch, steps)
+        finally:
+            if self.history is not None:                   # an epoch the guard refuses is the one whose record is wanted
+                self._drain_history(epoch)
 
     def _guard_report(self):
         """The optimizer's guard record when the guarded step is configured (a host synchronisation), else None."""

@@ -46,6 +46,9 @@ FUSED_FOCAL = True       # classification side (focal sums, class / cardinality 
 FUSED_MATCHED = True     # matched-pair losses through the HIP kernels on the GPU (False: the PyTorch formulation below)
 
 
+_PEEK_ZERO = {}          # device -> the zero LossDict.peek hands out for disabled losses
+
+
 class LossDict(dict):
     """The criterion's loss dictionary (same keys as the reference) that also remembers the [n_keys, n_layers] matrix its
     per-layer entries are views of, so that ``weighted_total`` is one multiply-and-sum instead of ~60 scalar kernels.
@@ -69,6 +72,19 @@ class LossDict(dict):
             dict.__setitem__(self, key, value)
             return value
         raise KeyError(key)
+
+    def peek(self, key):
+        """The value of ``self[key]``, to be read only (detached for the disabled losses), without creating a lazy entry: the
+        dictionary's key order -- what the training log prints in -- stays as it is."""
+        if dict.__contains__(self, key) or self.lazy is None or key not in self.lazy:
+            return dict.__getitem__(self, key)
+        i, l = self.lazy[key]
+        if i >= 0:
+            return self.mat[i, l]
+        zero = _PEEK_ZERO.get(self.mat.device)           # loss_tfl / loss_mask: one constant zero per device, made once (no fill per step)
+        if zero is None:
+            zero = _PEEK_ZERO[self.mat.device] = torch.zeros((), device=self.mat.device, dtype=torch.float32)
+        return zero
 
     def _all_keys(self):
         seen = list(dict.keys(self))

@@ -15,7 +15,7 @@ SYMBOLS = ("mono_bias_act_f32", "mono_bias_relu_maxpool_nhwc_f32", "mono_conv1x1
            "mono_relu_dropout_bwd_f32", "mono_matched_losses_fwd_f32", "mono_matched_losses_bwd_f32", "mono_ddn_loss_blocks",
            "mono_ddn_loss_fwd_f32", "mono_ddn_loss_bwd_f32", "mono_depth_expect_fwd_f32", "mono_depth_expect_bwd_f32", "mono_focal_fwd_f32", "mono_focal_bwd_f32", "mono_head_tail_fwd_f32", "mono_head_tail_bwd_f32", "mono_match_cost_f32", "mono_refine_reference_f32", "mono_relu_dropout_bwd_colsum_f32", "mono_sum_slices_f32", "mono_colsum_any_blocks", "mono_colsum_any_f32", "mono_relu_grad_mask3_f32", "mono_lsap_match_flat_f32",
            "mono_linear_wgrad_workspace", "mono_linear_wgrad_f32", "mono_colsum_levels_blocks", "mono_colsum_levels_f32", "mono_relu_grad_scale_f32",
-           "mono_set_deterministic", "mono_groupnorm_stats_doubles", "mono_groupnorm_part_doubles", "mono_grad_accumulate_f32", "mono_ema_update_f32")
+           "mono_set_deterministic", "mono_groupnorm_stats_doubles", "mono_groupnorm_part_doubles", "mono_grad_accumulate_f32", "mono_ema_update_f32", "mono_step_stats_f32")
 _lib = None
 
 
@@ -100,6 +100,8 @@ def load():
         lib.mono_grad_accumulate_f32.argtypes = [P, I, P]
         lib.mono_ema_update_f32.restype = I
         lib.mono_ema_update_f32.argtypes = [P, I, ctypes.c_float, P, P]
+        lib.mono_step_stats_f32.restype = I
+        lib.mono_step_stats_f32.argtypes = [P, P, P, I, I, P, P, P, P]
         lib.mono_colsum_strided_f32.restype = I
         lib.mono_colsum_strided_f32.argtypes = [P, P, P, I, LL, LL, I, P]
         lib.mono_colsum_levels_blocks.restype = I
@@ -859,6 +861,30 @@ class GradGuard:
         raw = self.record.cpu().numpy().view(np.uint8)
         return {"grad_norm": float(raw[0:4].view(np.float32)[0]), "coef": float(raw[4:8].view(np.float32)[0]),
                 "skip": int(raw[8:12].view(np.int32)[0]), "skipped_total": int(raw[16:24].view(np.int64)[0])}
+
+
+STATS_MAX_GROUPS = 64         # module groups one mono_step_stats_f32 call takes
+
+
+def step_stats(plans, groups, n_groups, record, partials, out):
+    """``mono_step_stats_f32`` over the refreshed ``FusedAdamWPlan`` tables ``plans``: per module group the sum of squares of the
+    gradients and of the parameters and the number of non-finite gradient elements, then norm, coef and skip of the guard record, as
+    ``3 * n_groups + 3`` doubles at the device address ``out``.  ``groups``: one device int32 tensor per plan, the group id of every
+    chunk (``plan.tensor`` tells the tensor a chunk belongs to).  ``record``: device address of the guard record or None.
+    ``partials``: float64 device scratch of at least 3 * sum(n_chunks) elements.  Two launches, nothing waits for the device."""
+    if not 1 <= len(plans) <= GUARD_MAX_GROUPS or len(groups) != len(plans):
+        raise ValueError("step_stats takes 1 to %d chunk tables and as many group arrays, not %d and %d" % (GUARD_MAX_GROUPS, len(plans), len(groups)))
+    if any(g.dtype != torch.int32 or g.numel() != p.n_chunks or g.device != p.device or not g.is_contiguous() for g, p in zip(groups, plans)):
+        raise ValueError("step_stats: a group array is not a contiguous int32 tensor of its table's chunk count on its device")
+    if partials.dtype != torch.float64 or partials.numel() < 3 * sum(p.n_chunks for p in plans):
+        raise ValueError("step_stats: partials must hold 3 * sum(n_chunks) float64")
+    tables = (ctypes.c_void_p * len(plans))(*[p.dev.data_ptr() for p in plans])
+    counts = (ctypes.c_int * len(plans))(*[p.n_chunks for p in plans])
+    gids = (ctypes.c_void_p * len(plans))(*[g.data_ptr() for g in groups])
+    with on_device(plans[0].device):
+        code = load().mono_step_stats_f32(tables, counts, gids, len(plans), n_groups, record, partials.data_ptr(), out, raw_stream())
+    if code:
+        raise RuntimeError("mono_step_stats_f32 failed with code %d" % code)
 
 
 FUSED_ACCUMULATE = True       # gradient accumulation over micro-batches through mono_grad_accumulate_f32 (False: autograd's in-place adds)
