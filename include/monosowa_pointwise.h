@@ -265,6 +265,23 @@ int mono_focal_fwd_f32(const float *logits, const long long *idx, const long lon
 int mono_focal_bwd_f32(const float *logits, const long long *idx, const long long *labels, const float *grad_out, float *grad_logits,
                        int NL, int B, int Q, int C, int K, float alpha, float gamma, void *stream);
 
+/* Label audit (monosowa_amd/label_audit.py): what the matched-pair terms above say about every single LABEL.  The predictions and idx
+ * [3, NL, K] are those of mono_matched_losses_fwd_f32 and mono_focal_fwd_f32; labels [T] int64.  out: [T, 9] float64; row t covers the
+ * pairs k of layer `layer` with idx[2][layer][k] == t:
+ *     0 mean |dcx| + |dcy|      1 mean l/r/t/b L1      2 mean 1 - GIoU      3 mean 1.4142 exp(-s) |d - d*| + s      4 mean |d - d*|
+ *     5 mean sum |size - size*| (plain L1, no compensation weight)      6 mean heading cross entropy + residual L1
+ *     7 mean sigmoid(logit[label class]) of the matched query (NaN for a class outside [0, C))      8 number of pairs
+ * Every per-pair term is the float32 expression of mono_matched_losses_fwd_f32, widened to double, summed in double and divided by the
+ * count in double.  A label without a pair gets nine exact zeros; NaN and +-Inf stay in the row of their label.  A pair whose image or
+ * query index lies outside [0, B) x [0, Q) is counted nowhere.  One launch, one wavefront per label, a fixed shuffle tree, no atomics:
+ * the same inputs give the same bytes wherever out lies.  Nothing but out[0 : 9 T] is written.
+ * Returns -1 for a NULL pointer (idx may be NULL with K == 0), -2 for layer outside [0, NL), NL, B, Q or C < 1, K or T < 0 or C > 255;
+ * T == 0 launches nothing and returns 0. */
+int mono_label_audit_f32(const float *logits, const float *boxes, const float *depth, const float *dims, const float *angle,
+                         const long long *idx, const long long *labels, const float *t_box, const float *t_depth,
+                         const float *t_size, const long long *t_bin, const float *t_res, double *out, int NL, int B, int Q, int C,
+                         int K, int T, int layer, void *stream);
+
 /* The Hungarian matcher's cost, restricted to each image's own targets (reference matcher.py:53-88: focal-style class cost, L1
  * of the projected 3-D centre and of (l, r, t, b), generalised IoU, weighted): logits [NL, B, Q, C], boxes [NL, B, Q, 6] (cx, cy, l,
  * r, t, b); labels [T] int64 and tboxes [T, 6] of the batch's concatenated targets; cols [B, N] int64 = flat target of slot j of

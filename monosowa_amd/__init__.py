@@ -10,4 +10,7 @@ def __getattr__(name):
     if name == "StepHistory":               # the per-step training record (monosowa_amd/history.py)
         from .history import StepHistory
         return StepHistory
+    if name == "LabelAudit":                # the per-label disagreement record (monosowa_amd/label_audit.py)
+        from .label_audit import LabelAudit
+        return LabelAudit
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

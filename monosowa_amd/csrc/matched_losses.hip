@@ -167,6 +167,77 @@ __global__ __launch_bounds__(256) void matched_bwd_kernel(const MatchedArgs a, c
   }
 }
 
+// ---- label audit (monosowa_amd/label_audit.py): the terms above per LABEL instead of per layer -----------------------------------------
+//   out[t] = means over the pairs of one layer that are matched to flat target t of
+//            { |dcx| + |dcy|, l/r/t/b L1, 1 - GIoU, Laplacian depth term, |d - d*|, sum |s - s*|, heading CE + residual L1,
+//              sigmoid(logit of the label's class) }, then the number of pairs -- nine doubles.
+// Every term is matched_fwd_kernel's float32 expression on the same load_pair; it is widened to double, added in double and divided
+// by the count in double.  One wavefront per label: its lanes stride over k (fixed order per lane), a fixed xor tree adds the lanes.
+// No atomics, nothing depends on where out lies.  A label without a pair: nine zeros.  A pair whose image or query index lies
+// outside [0, B) x [0, Q) is counted nowhere (nothing is read through it).
+constexpr int kAuditCols = 9;
+constexpr int kAuditLabelsPerBlock = 4;               // wavefronts of a 256-thread workgroup
+
+struct AuditArgs {
+  MatchedArgs m;
+  const float *logits;                // [NL, B, Q, C]
+  const long long *labels;            // [T] class of every target
+  int C, T, layer;
+};
+
+__global__ __launch_bounds__(256) void label_audit_kernel(const AuditArgs a, double *__restrict__ out) {
+  const int t = blockIdx.x * kAuditLabelsPerBlock + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (t >= a.T) return;                               // whole wavefronts leave: the shuffles below see all 64 lanes
+  const int l = a.layer;
+  const long long stride = (long long)a.m.NL * a.m.K;
+  const long long *bi = a.m.idx + (long long)l * a.m.K, *qi = bi + stride, *ti = bi + 2 * stride;
+  const long long cls = a.labels[t];
+  double s[kAuditCols - 1] = {0., 0., 0., 0., 0., 0., 0., 0.}, n = 0.;
+  for (int k = lane; k < a.m.K; k += 64) {
+    if (ti[k] != (long long)t) continue;
+    if ((unsigned long long)bi[k] >= (unsigned long long)a.m.B || (unsigned long long)qi[k] >= (unsigned long long)a.m.Q) continue;
+    const Pair p = load_pair(a.m, l, k);
+    s[0] += (double)(fabsf(p.box[0] - p.tbox[0]) + fabsf(p.box[1] - p.tbox[1]));
+    s[1] += (double)((fabsf(p.box[2] - p.tbox[2]) + fabsf(p.box[3] - p.tbox[3])) + (fabsf(p.box[4] - p.tbox[4]) + fabsf(p.box[5] - p.tbox[5])));
+    float xa[4], xb[4], g[4];
+    to_xyxy(p.box, xa);
+    to_xyxy(p.tbox, xb);
+    s[2] += (double)(1.f - giou_grad(xa, xb, g));
+    s[3] += (double)(1.4142f * expf(-p.dep[1]) * fabsf(p.dep[0] - p.tdep) + p.dep[1]);
+    s[4] += (double)fabsf(p.dep[0] - p.tdep);
+    float l1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) l1 += fabsf(p.dim[i] - p.tdim[i]);
+    s[5] += (double)l1;
+    float mx = p.ang[0];
+#pragma unroll
+    for (int i = 1; i < 12; ++i) mx = fmaxf(mx, p.ang[i]);
+    float se = 0.f;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) se += expf(p.ang[i] - mx);
+    float logit_t = 0.f, res_p = 0.f;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) { if (i == p.bin) { logit_t = p.ang[i]; res_p = p.ang[12 + i]; } }
+    s[6] += (double)((logf(se) + mx - logit_t) + fabsf(res_p - p.tres));
+    // a class outside [0, C) names no logit: NaN, nothing is read
+    const float x = (cls >= 0 && cls < a.C) ? a.logits[p.row * a.C + cls] : __builtin_nanf("");
+    s[7] += (double)(1.f / (1.f + expf(-x)));
+    n += 1.;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int j = 0; j < kAuditCols - 1; ++j) s[j] += __shfl_xor(s[j], o);
+    n += __shfl_xor(n, o);
+  }
+  if (lane == 0) {
+    double *row = out + (long long)t * kAuditCols;
+#pragma unroll
+    for (int j = 0; j < kAuditCols - 1; ++j) row[j] = n > 0. ? s[j] / n : 0.;
+    row[kAuditCols - 1] = n;
+  }
+}
+
 // ---- classification side of the criterion for all decoder layers (monodetr.py:396-449, sigmoid_focal_loss :302-330) -------------
 //   out[l] = { sum over (image, query, class) of the sigmoid focal loss against the matched one-hot targets,
 //              class_error = 100 - top-1 accuracy of the matched queries in %,

@@ -1481,6 +1481,23 @@ int mono_focal_bwd_f32(const float *logits, const long long *idx, const long lon
 }
 
 
+// ---- label audit (matched_losses.hip): per flat target the mean terms of its matched pairs of one layer, nine doubles ------------
+int mono_label_audit_f32(const float *logits, const float *boxes, const float *depth, const float *dims, const float *angle,
+                         const long long *idx, const long long *labels, const float *t_box, const float *t_depth,
+                         const float *t_size, const long long *t_bin, const float *t_res, double *out, int NL, int B, int Q, int C,
+                         int K, int T, int layer, void *stream) {
+  if (!logits || !boxes || !depth || !dims || !angle || !labels || !t_box || !t_depth || !t_size || !t_bin || !t_res || !out ||
+      (K > 0 && !idx))
+    return -1;
+  if (NL <= 0 || B <= 0 || Q <= 0 || C <= 0 || C > 255 || K < 0 || T < 0 || layer < 0 || layer >= NL) return -2;
+  if (T == 0) return 0;
+  const mono::AuditArgs a{{boxes, depth, dims, angle, idx, t_box, t_depth, t_size, t_res, t_bin, NL, B, Q, K}, logits, labels, C, T, layer};
+  const int blocks = (T + mono::kAuditLabelsPerBlock - 1) / mono::kAuditLabelsPerBlock;
+  mono::label_audit_kernel<<<blocks, 64 * mono::kAuditLabelsPerBlock, 0, (hipStream_t)stream>>>(a, out);
+  return (int)hipGetLastError();
+}
+
+
 // ---- the matcher's per-image cost blocks (matched_losses.hip) ------------------------------------------------------------------
 int mono_match_cost_f32(const float *logits, const float *boxes, const long long *labels, const float *tboxes, const long long *cols,
                         float *out, int NL, int B, int Q, int C, int N, float w_class, float w_3d, float w_bbox, float w_giou,

@@ -25,6 +25,14 @@ checkpoint naming.  Differences that do not change results:
   it; non-finite numbers as the strings "nan", "inf", "-inf") and logs the epoch means of the weighted loss terms, the median and
   maximum of the global gradient norm and one line per step that had non-finite gradients.  Absent, None or false: nothing is built,
   allocated, launched, written or logged; nothing is added to a checkpoint either way.
+* ``trainer.label_audit: true`` (optional, absent from the shipped config): a per-label record kept on the device
+  (monosowa_amd/label_audit.py) -- for every label of every batch the mean of each matched-pair loss term over its ``group_num`` pairs of
+  the final decoder layer, the matched queries' score and the number of pairs -- by one launch per forward, without a synchronisation in
+  the step.  It describes the forward, so a step the guard skipped is recorded like any other.  It is read once per epoch, beside the
+  history: every rank writes ``<output_dir>/label_audit/epoch_%03d.npz`` (``epoch_%03d.rankR.npz`` under DDP; no collective is added)
+  and rank 0 logs the number of labels seen and the median and maximum of their |d - d*|.  ``tools/label_audit.py report`` ranks the
+  labels over the epochs.  Absent, None or false: nothing is built, allocated, launched, written or logged; the checkpoint is the same
+  either way.
 """
 import contextlib
 import math
@@ -125,6 +133,8 @@ class Trainer(object):
         self.history = None              # StepHistory with trainer.history, built below once the model is where it trains
         self._history_step = 0           # optimizer steps committed in the current epoch
         self._history_fresh = not cfg.get("resume_model", None)      # the first write of this run truncates history.jsonl
+        label_audit = self._label_audit_flag(cfg.get("label_audit"))
+        self.label_audit = None          # LabelAudit with trainer.label_audit, built below on the device the model trains on
 
         if cfg.get("pretrain_model"):
             assert os.path.exists(cfg["pretrain_model"])
@@ -142,6 +152,10 @@ class Trainer(object):
             from ..history import StepHistory
             steps = -(-len(train_loader) // self.accum_steps)          # optimizer steps of an epoch: never a drain inside one
             self.history = StepHistory(self.model, self.detr_loss.weight_dict, max(steps, 1))
+        if label_audit:
+            from ..label_audit import LabelAudit
+            self.label_audit = LabelAudit(self._label_audit_rows(train_loader), self.device)
+            self.detr_loss.audit = self.label_audit
         if resume is not None:
             self.epoch, self.best_result, self.best_epoch = load_checkpoint(
                 model=self.model, optimizer=self.optimizer, filename=resume,
@@ -225,6 +239,43 @@ class Trainer(object):
             raise ValueError("trainer.history = %r is not a bool (absent, None or false: off)" % (value,))
         return value
 
+    @staticmethod
+    def _label_audit_flag(value):
+        """``trainer.label_audit``: False for absent, None or false, True for true; anything else is refused."""
+        if value is None:
+            return False
+        if not isinstance(value, bool):
+            raise ValueError("trainer.label_audit = %r is not a bool (absent, None or false: off)" % (value,))
+        return value
+
+    @staticmethod
+    def _label_audit_rows(train_loader):
+        """Rows of the audit's ring: the labels an epoch can hold, so that the ring is never drained inside one -- ``len(dataset) x
+        max_objs`` when the loader exposes both, else the loader's ``len x batch_size x 50``."""
+        dataset = getattr(train_loader, "dataset", None)
+        max_objs = getattr(dataset, "max_objs", None)
+        if dataset is not None and isinstance(max_objs, int) and max_objs > 0 and hasattr(dataset, "__len__"):
+            return max(len(dataset) * max_objs, 1)
+        return max(len(train_loader) * int(getattr(train_loader, "batch_size", None) or 1) * 50, 1)
+
+    def _drain_label_audit(self, epoch):
+        """End of an epoch with ``trainer.label_audit``: the ring to the host (the one synchronisation of the record), every rank
+        writes its own file, rank 0 logs the summary.  No collective."""
+        from ..label_audit import COLUMNS, save
+        record = self.label_audit.drain()
+        ranked = misc.is_dist_avail_and_initialized() and misc.get_world_size() > 1
+        name = "epoch_%03d.rank%d.npz" % (epoch, misc.get_rank()) if ranked else "epoch_%03d.npz" % epoch
+        save(os.path.join(self.output_dir, "label_audit", name), record)
+        if not misc.is_main_process():
+            return
+        err = record["values"][:, COLUMNS.index("depth_abs")]
+        if len(err):
+            with np.errstate(invalid="ignore"):
+                self.logger.info("Epoch {}: label audit: {} labels seen, |d - d*| median: {:.4g}, max: {:.4g}".format(
+                    epoch, len(err), float(np.median(err)), float(np.max(err))))
+        else:
+            self.logger.info("Epoch {}: label audit: 0 labels seen".format(epoch))
+
     def _history_commit(self, micro_batches):
         self.history.commit(self.optimizer, epoch=self.epoch, step=self._history_step, lr=self.optimizer.param_groups[0]["lr"],
                             micro_batches=micro_batches)
@@ -276,6 +327,8 @@ class Trainer(object):
         """One optimizer step on a device-resident batch; returns (total loss tensor, loss dict)."""
         img_sizes = targets["img_size"]
         target_list = self.prepare_targets(targets, inputs.shape[0])
+        if self.label_audit is not None:
+            self._audit_begin(targets, info, inputs.shape[0])
         self.optimizer.zero_grad(set_to_none=True)
         outputs = self.model(inputs, calibs, target_list, img_sizes, dn_args=None)
         loss_dict = self.detr_loss(outputs, target_list, None, info)
@@ -290,6 +343,12 @@ class Trainer(object):
         if self.ema is not None:
             self.ema.update(self.optimizer)
         return total, loss_dict
+
+    def _audit_begin(self, targets, info, batch_size):
+        """Reserves the audit's rows for the forward that follows and names them: ``info["img_id"]`` and the host object mask."""
+        if info is None or "img_id" not in info:
+            raise ValueError("trainer.label_audit names every label by its image: the batch's info needs \"img_id\"")
+        self.label_audit.begin_batch(np.asarray(info["img_id"]).reshape(-1)[:batch_size], targets["mask_2d"], epoch=self.epoch)
 
     @staticmethod
     def _accum_steps(global_batch, train_loader):
@@ -353,6 +412,8 @@ class Trainer(object):
         for k, raw in enumerate(raws):
             inputs, calibs, targets, info = stage_batch(raw, self.device)
             target_list = self.prepare_targets(targets, inputs.shape[0])
+            if self.label_audit is not None:
+                self._audit_begin(targets, info, inputs.shape[0])
             with (self.model.no_sync() if ddp and k < K - 1 else contextlib.nullcontext()):
                 outputs = self.model(inputs, calibs, target_list, targets["img_size"], dn_args=None)
                 loss_dict = self.detr_loss(outputs, target_list, None, info, num_boxes=num_boxes)
@@ -414,6 +475,8 @@ class Trainer(object):
         finally:
             if self.history is not None:                   # an epoch the guard refuses is the one whose record is wanted
                 self._drain_history(epoch)
+            if self.label_audit is not None:
+                self._drain_label_audit(epoch)
 
     def _guard_report(self):
         """The optimizer's guard record when the guarded step is configured (a host synchronisation), else None."""

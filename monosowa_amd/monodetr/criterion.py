@@ -147,6 +147,10 @@ def weighted_total(loss_dict, weight_dict):
 
 
 class SetCriterion(nn.Module):
+    # a monosowa_amd.label_audit.LabelAudit: both formulations hand it the final layer's predictions and matched pairs once the pairs are
+    # known (``observe``: one launch, nothing waits); None: nothing is launched, allocated or read for it
+    audit = None
+
     def __init__(self, num_classes, matcher, weight_dict, focal_alpha, losses, group_num=11, cfg=None,
                  depth_map_size=(80, 24), fast=True):
         super().__init__()
@@ -362,6 +366,10 @@ class SetCriterion(nn.Module):
         # from the matcher's pinned buffer the copy is queued behind the depth-map kernels still running; from pageable memory
         # the host would wait for them here, with the whole backward still to enqueue
         idx = (idx_host if torch.is_tensor(idx_host) else torch.from_numpy(idx_host)).to(dev, non_blocking=True)
+        if self.audit is not None:                                             # layer 0 of the stack is the model's final output
+            with torch.no_grad():
+                self.audit.observe(*[t.detach() for t in (prep if fused_tail else (logits, boxes, depth, dims, angle))], idx,
+                                   dict(flat, labels=labels64) if fused_tail else flat, layer=0)
         if fused_tail and K > 0 and focal_classification_supported(logits, idx):
             # the whole criterion behind the matching in four launches: classification side + matched-pair losses, forward
             # and backward (csrc/matched_losses.hip), the loss matrix in two more
@@ -452,10 +460,28 @@ class SetCriterion(nn.Module):
         return losses
 
     # ------------------------------------------------------------------ reference formulation
+    def _observe_layerwise(self, outputs, targets, indices):
+        """``audit.observe`` with the final layer's per-image ``indices`` as the flat [3, 1, K] index tensor ``forward_fast`` builds:
+        (image, query, offset of the image's targets + target), images in order."""
+        dev = outputs["pred_logits"].device
+        offs = np.concatenate([[0], np.cumsum([len(t["labels"]) for t in targets])[:-1]]).astype(np.int64)
+        idx = torch.stack([torch.cat([torch.full_like(src, b) for b, (src, _) in enumerate(indices)]),
+                           torch.cat([src for src, _ in indices]),
+                           torch.cat([tgt + int(offs[b]) for b, (_, tgt) in enumerate(indices)])]).view(3, 1, -1).to(dev)
+        flat = getattr(targets, "flat", None)
+        keys = ("labels", "boxes_3d", "depth", "size_3d", "heading_bin", "heading_res")
+        if flat is None or any(k not in flat for k in keys):
+            flat = {k: torch.cat([t[k] for t in targets], dim=0) for k in keys}
+        with torch.no_grad():
+            self.audit.observe(*[outputs[k].detach().unsqueeze(0) for k in ("pred_logits", "pred_boxes", "pred_depth", "pred_3d_dim", "pred_angle")],
+                               idx, flat, layer=0)
+
     def forward_layerwise(self, outputs, targets, mask_dict=None, info=None, num_boxes=None):
         outputs_without_aux = {k: v for k, v in outputs.items() if k != "aux_outputs"}
         group_num = self.group_num if self.training else 1
         indices = self.matcher(outputs_without_aux, targets, group_num=group_num)
+        if self.audit is not None:
+            self._observe_layerwise(outputs_without_aux, targets, indices)
 
         if num_boxes is None:
             num_boxes = sum(len(t["labels"]) for t in targets) * group_num

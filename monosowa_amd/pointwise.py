@@ -15,7 +15,8 @@ SYMBOLS = ("mono_bias_act_f32", "mono_bias_relu_maxpool_nhwc_f32", "mono_conv1x1
            "mono_relu_dropout_bwd_f32", "mono_matched_losses_fwd_f32", "mono_matched_losses_bwd_f32", "mono_ddn_loss_blocks",
            "mono_ddn_loss_fwd_f32", "mono_ddn_loss_bwd_f32", "mono_depth_expect_fwd_f32", "mono_depth_expect_bwd_f32", "mono_focal_fwd_f32", "mono_focal_bwd_f32", "mono_head_tail_fwd_f32", "mono_head_tail_bwd_f32", "mono_match_cost_f32", "mono_refine_reference_f32", "mono_relu_dropout_bwd_colsum_f32", "mono_sum_slices_f32", "mono_colsum_any_blocks", "mono_colsum_any_f32", "mono_relu_grad_mask3_f32", "mono_lsap_match_flat_f32",
            "mono_linear_wgrad_workspace", "mono_linear_wgrad_f32", "mono_colsum_levels_blocks", "mono_colsum_levels_f32", "mono_relu_grad_scale_f32",
-           "mono_set_deterministic", "mono_groupnorm_stats_doubles", "mono_groupnorm_part_doubles", "mono_grad_accumulate_f32", "mono_ema_update_f32", "mono_step_stats_f32")
+           "mono_set_deterministic", "mono_groupnorm_stats_doubles", "mono_groupnorm_part_doubles", "mono_grad_accumulate_f32", "mono_ema_update_f32", "mono_step_stats_f32",
+           "mono_label_audit_f32")
 _lib = None
 
 
@@ -102,6 +103,8 @@ def load():
         lib.mono_ema_update_f32.argtypes = [P, I, ctypes.c_float, P, P]
         lib.mono_step_stats_f32.restype = I
         lib.mono_step_stats_f32.argtypes = [P, P, P, I, I, P, P, P, P]
+        lib.mono_label_audit_f32.restype = I
+        lib.mono_label_audit_f32.argtypes = [P] * 13 + [I] * 7 + [P]
         lib.mono_colsum_strided_f32.restype = I
         lib.mono_colsum_strided_f32.argtypes = [P, P, P, I, LL, LL, I, P]
         lib.mono_colsum_levels_blocks.restype = I
@@ -1260,6 +1263,23 @@ def focal_classification(logits, idx, labels, sizes, alpha, gamma=2.0):
     class error in % and the cardinality error (monodetr.py:396-449) -- one HIP launch each way."""
     return _FocalClassification.apply(logits.contiguous(), idx.contiguous(), labels.to(torch.int64).contiguous(),
                                       sizes.to(torch.float32).contiguous(), float(alpha), float(gamma))
+
+
+# ---- label audit (csrc/matched_losses.hip) --------------------------------------------------------------------------------------------
+def label_audit_supported(logits):
+    return logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 4 and logits.shape[3] <= 255
+
+
+def label_audit(logits, boxes, depth, dims, angle, idx, labels, t_box, t_depth, t_size, t_bin, t_res, out, T, layer=0):
+    """``mono_label_audit_f32``: per flat target the means of the matched-pair terms of layer ``layer`` and the number of its pairs, as
+    ``[T, 9]`` doubles (``label_audit.COLUMNS``) at the device address ``out``.  The tensors are the contiguous float32 / int64 ones the
+    fused criterion hands its kernels.  One launch, nothing waits for the device."""
+    NL, B, Q, C = logits.shape
+    tensors = (logits, boxes, depth, dims, angle, idx, labels, t_box, t_depth, t_size, t_bin, t_res)
+    with on_device(logits.device):
+        code = load().mono_label_audit_f32(*[t.data_ptr() for t in tensors], out, NL, B, Q, C, idx.size(2), T, layer, raw_stream())
+    if code:
+        raise RuntimeError("mono_label_audit_f32 failed with code %d" % code)
 
 
 # ---- the matcher's cost blocks (csrc/matched_losses.hip) ---------------------------------------------------------------------------
