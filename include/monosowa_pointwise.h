@@ -100,6 +100,19 @@ int mono_matched_losses_bwd_f32(const float *boxes, const float *depth, const fl
                                 const long long *t_bin, const float *t_res, const float *comp, const float *grad_out,
                                 float *g_boxes, float *g_depth, float *g_dims, float *g_angle, int NL, int B, int Q, int K,
                                 void *stream);
+/* The two above with per-label weights t_weight [T] (float32, finite, >= 0, may exceed 1): the pair of flat target t enters every
+ * per-layer sum as fma(t_weight[t], term, sum); comp [NL] = sum w |s - s*| / sum w |s - s*| / s*; the backward scales the pair's
+ * gradients by t_weight[t] (0: zeros are stored).  All weights 1: the bytes of the unweighted entry points; all 0.5: exactly half.
+ * Same launch shape (one workgroup per layer), same plain stores into zeroed gradients, same error codes. */
+int mono_matched_losses_weighted_fwd_f32(const float *boxes, const float *depth, const float *dims, const float *angle,
+                                         const long long *idx, const float *t_box, const float *t_depth, const float *t_size,
+                                         const long long *t_bin, const float *t_res, const float *t_weight, float *out, float *comp,
+                                         int NL, int B, int Q, int K, void *stream);
+int mono_matched_losses_weighted_bwd_f32(const float *boxes, const float *depth, const float *dims, const float *angle,
+                                         const long long *idx, const float *t_box, const float *t_depth, const float *t_size,
+                                         const long long *t_bin, const float *t_res, const float *t_weight, const float *comp,
+                                         const float *grad_out, float *g_boxes, float *g_depth, float *g_dims, float *g_angle, int NL,
+                                         int B, int Q, int K, void *stream);
 
 /* One step of the reference's AdamW variant (lib/helpers/optimizer_helper.py:69-129: eps added to sqrt(v) before the
  * bias correction, decay scaled by the corrected step size) over all parameters in one launch.
@@ -246,6 +259,18 @@ int mono_ddn_loss_bwd_f32(const float *logits, const float *boxes, const float *
                           const float *grad_total, float *grad_logits, int B, int C, int H, int W, int N, long long sb, long long sc,
                           long long sp, float alpha, float gamma, float fg_weight, float bg_weight, float depth_min, float depth_max,
                           void *stream);
+/* The two above with per-box weights box_weight [B, N] (padded like depth; float32, finite, >= 0).  The target depth of a pixel is
+ * unchanged (the nearest valid covering box; a box of weight 0 still paints); a foreground pixel weighs fg_weight * box_weight[i], i
+ * the lowest slot among the covering boxes of that nearest depth (slot order, strict <).  Background pixels and the divisor are
+ * unchanged.  All weights 1: the bytes of the unweighted entry points. */
+int mono_ddn_loss_weighted_fwd_f32(const float *logits, const float *boxes, const float *depth, const unsigned char *valid,
+                                   const float *box_weight, float *partial, int B, int C, int H, int W, int N, long long sb,
+                                   long long sc, long long sp, float alpha, float gamma, float fg_weight, float bg_weight,
+                                   float depth_min, float depth_max, void *stream);
+int mono_ddn_loss_weighted_bwd_f32(const float *logits, const float *boxes, const float *depth, const unsigned char *valid,
+                                   const float *box_weight, const float *grad_total, float *grad_logits, int B, int C, int H, int W,
+                                   int N, long long sb, long long sc, long long sp, float alpha, float gamma, float fg_weight,
+                                   float bg_weight, float depth_min, float depth_max, void *stream);
 
 /* Expected depth of the bin distribution (depth_predictor/depth_predictor.py:90-91): out [B, H, W] = sum_c softmax(logits)_c *
  * values[c]; logits [B, C, H, W] with (batch, channel, pixel) strides as above.  backward: grad_logits (same strides) =
@@ -264,6 +289,18 @@ int mono_focal_fwd_f32(const float *logits, const long long *idx, const long lon
                        int B, int Q, int C, int K, float alpha, float gamma, void *stream);
 int mono_focal_bwd_f32(const float *logits, const long long *idx, const long long *labels, const float *grad_out, float *grad_logits,
                        int NL, int B, int Q, int C, int K, float alpha, float gamma, void *stream);
+/* The two above with per-label weights t_weight [T]: all C terms (and gradients) of a cell matched to flat target t are multiplied by
+ * t_weight[t], unmatched cells keep factor 1, so a weight of 0 makes the label's queries don't-care queries.  class_error and
+ * cardinality_error stay unweighted.  All weights 1: the bytes of the unweighted entry points.
+ * Limits: C <= 255, B <= 256, B * Q <= mono_focal_weighted_max_cells() = 16384 (a cell keeps its pair beside its class in LDS),
+ * K < 65535. */
+int mono_focal_weighted_max_cells(void);
+int mono_focal_weighted_fwd_f32(const float *logits, const long long *idx, const long long *labels, const float *sizes,
+                                const float *t_weight, float *out, int NL, int B, int Q, int C, int K, float alpha, float gamma,
+                                void *stream);
+int mono_focal_weighted_bwd_f32(const float *logits, const long long *idx, const long long *labels, const float *t_weight,
+                                const float *grad_out, float *grad_logits, int NL, int B, int Q, int C, int K, float alpha, float gamma,
+                                void *stream);
 
 /* Label audit (monosowa_amd/label_audit.py): what the matched-pair terms above say about every single LABEL.  The predictions and idx
  * [3, NL, K] are those of mono_matched_losses_fwd_f32 and mono_focal_fwd_f32; labels [T] int64.  out: [T, 9] float64; row t covers the

@@ -21,10 +21,14 @@ struct DdnParams {
   float alpha, gamma, fg_weight, bg_weight, depth_min, depth_max, eps;
 };
 
-// target bin and weight of pixel (b, y, x): boxes [B, N, 4] = xyxy in depth-map pixels (float), depth [B, N], valid [B, N]
+// target bin and weight of pixel (b, y, x): boxes [B, N, 4] = xyxy in depth-map pixels (float), depth [B, N], valid [B, N].
+// BW: per-box weights bw [B, N] (nullptr and never read without BW); a foreground pixel weighs fg_weight * bw of the LOWEST slot among
+// the covering boxes of the nearest depth (slot order, strict <).  A box of weight 0 paints its depth like any other.
+template <bool BW>
 __device__ __forceinline__ void ddn_target(const DdnParams &p, const float *__restrict__ boxes, const float *__restrict__ depth,
-                                           const unsigned char *__restrict__ valid, int b, int y, int x, int &bin, float &weight) {
-  float nearest = INFINITY;
+                                           const unsigned char *__restrict__ valid, const float *__restrict__ bw, int b, int y, int x,
+                                           int &bin, float &weight) {
+  float nearest = INFINITY, wbox = 1.f;
   bool fg = false;
   for (int i = 0; i < p.N; ++i) {
     if (!valid[b * p.N + i]) continue;
@@ -34,8 +38,13 @@ __device__ __forceinline__ void ddn_target(const DdnParams &p, const float *__re
     auto norm = [](long long a, int n) { a = a < 0 ? a + n : a; return a < 0 ? 0LL : (a > n ? (long long)n : a); };
     u1 = norm(u1, p.W); u2 = norm(u2, p.W); v1 = norm(v1, p.H); v2 = norm(v2, p.H);
     if (y >= v1 && y < v2 && x >= u1 && x < u2) {
+      if constexpr (BW) {
+        const float dv = depth[b * p.N + i];
+        if (dv < nearest || (!fg && dv == nearest)) { nearest = dv; wbox = bw[b * p.N + i]; }
+      } else {
+        nearest = fminf(nearest, depth[b * p.N + i]);
+      }
       fg = true;
-      nearest = fminf(nearest, depth[b * p.N + i]);
     }
   }
   const float d = fg ? nearest : 0.f;
@@ -44,7 +53,8 @@ __device__ __forceinline__ void ddn_target(const DdnParams &p, const float *__re
   const float idx = -0.5f + 0.5f * sqrtf(1.f + 8.f * (d - p.depth_min) / bin_size);
   const bool bad = (idx < 0.f) || (idx > (float)num_bins) || !isfinite(idx);
   bin = bad ? num_bins : (int)idx;
-  weight = fg ? p.fg_weight : p.bg_weight;
+  if constexpr (BW) weight = fg ? p.fg_weight * wbox : p.bg_weight;
+  else weight = fg ? p.fg_weight : p.bg_weight;
 }
 
 constexpr int kDdnLanes = 8;          // lanes of one pixel: lane j takes bins j, j + 8, ... (an aligned group of 8 lanes of a wave)
@@ -56,9 +66,10 @@ __device__ __forceinline__ float group8_sum(float v) {
 }
 
 // partial[block] = sum over the block's pixels of weight * pixel loss   (the host sums the partials and divides)
+template <bool BW>
 __global__ __launch_bounds__(256) void ddn_loss_fwd_kernel(const float *__restrict__ logits, const float *__restrict__ boxes,
                                                            const float *__restrict__ depth, const unsigned char *__restrict__ valid,
-                                                           float *__restrict__ partial, const DdnParams p) {
+                                                           const float *__restrict__ bw, float *__restrict__ partial, const DdnParams p) {
   __shared__ float red[4];
   const int slot = blockIdx.x * 256 + threadIdx.x, n_pix = p.B * p.H * p.W;
   const int sub = slot & (kDdnLanes - 1);
@@ -66,7 +77,7 @@ __global__ __launch_bounds__(256) void ddn_loss_fwd_kernel(const float *__restri
   const int pix = live ? slot / kDdnLanes : n_pix - 1;                 // (dead lanes shadow the last pixel: the shuffles stay uniform)
   const int b = pix / (p.H * p.W), hw = pix - b * p.H * p.W, y = hw / p.W, x = hw - y * p.W;
   int bin; float weight;
-  ddn_target(p, boxes, depth, valid, b, y, x, bin, weight);
+  ddn_target<BW>(p, boxes, depth, valid, bw, b, y, x, bin, weight);
   const float *z = logits + b * p.sb + hw * p.sp;
   float mx = -INFINITY;
   for (int c = sub; c < p.C; c += kDdnLanes) mx = fmaxf(mx, z[c * p.sc]);
@@ -96,17 +107,18 @@ __device__ __forceinline__ float focal_dp_times_p(const DdnParams &p, float ls, 
 }
 
 // grad_logits = g_scale * weight * d(pixel loss) / d logits, g_scale = grad of the total / number of pixels (device scalar)
+template <bool BW>
 __global__ __launch_bounds__(256) void ddn_loss_bwd_kernel(const float *__restrict__ logits, const float *__restrict__ boxes,
                                                            const float *__restrict__ depth, const unsigned char *__restrict__ valid,
-                                                           const float *__restrict__ grad_total, float *__restrict__ grad_logits,
-                                                           const DdnParams p) {
+                                                           const float *__restrict__ bw, const float *__restrict__ grad_total,
+                                                           float *__restrict__ grad_logits, const DdnParams p) {
   const int slot = blockIdx.x * 256 + threadIdx.x, n_pix = p.B * p.H * p.W;
   const int sub = slot & (kDdnLanes - 1);
   const bool live = slot / kDdnLanes < n_pix;
   const int pix = live ? slot / kDdnLanes : n_pix - 1;
   const int b = pix / (p.H * p.W), hw = pix - b * p.H * p.W, y = hw / p.W, x = hw - y * p.W;
   int bin; float weight;
-  ddn_target(p, boxes, depth, valid, b, y, x, bin, weight);
+  ddn_target<BW>(p, boxes, depth, valid, bw, b, y, x, bin, weight);
   const float *z = logits + b * p.sb + hw * p.sp;
   float *gz = grad_logits + b * p.sb + hw * p.sp;
   float mx = -INFINITY;

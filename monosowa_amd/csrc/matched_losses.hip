@@ -58,6 +58,7 @@ struct Pair {
   float box[6], tbox[6], dep[2], tdep, dim[3], tdim[3], ang[24], tres;
   int bin;
   long long row;      // (l * B + b) * Q + q
+  long long t;        // flat target
 };
 
 __device__ __forceinline__ Pair load_pair(const MatchedArgs &a, int l, int k) {
@@ -66,6 +67,7 @@ __device__ __forceinline__ Pair load_pair(const MatchedArgs &a, int l, int k) {
   const long long stride = (long long)a.NL * a.K;
   const long long b = ip[0], q = ip[stride], t = ip[2 * stride];
   p.row = ((long long)l * a.B + b) * a.Q + q;
+  p.t = t;
 #pragma unroll
   for (int i = 0; i < 6; ++i) { p.box[i] = a.boxes[p.row * 6 + i]; p.tbox[i] = a.t_box[t * 6 + i]; }
   p.dep[0] = a.depth[p.row * 2]; p.dep[1] = a.depth[p.row * 2 + 1]; p.tdep = a.t_depth[t];
@@ -82,25 +84,38 @@ __device__ __forceinline__ void to_xyxy(const float c[6], float o[4]) {
   o[0] = c[0] - c[2]; o[1] = c[1] - c[4]; o[2] = c[0] + c[3]; o[3] = c[1] + c[5];
 }
 
-// out[l] = {center, bbox, giou, depth, dim, angle} sums; comp[l] = sum |s - s*| / sum |s - s*| / s*
-__global__ __launch_bounds__(256) void matched_fwd_kernel(const MatchedArgs a, float *__restrict__ out, float *__restrict__ comp) {
+// Per-label weights (W; tw [T], finite, >= 0; nullptr and never read without W): the pair of flat target t enters every sum as
+// fma(w_t, term, sum) -- one rounding, so all weights 1 give the unweighted bytes and all weights 0.5 exactly half of them.
+template <bool W>
+__device__ __forceinline__ float wacc(float w, float term, float acc) {
+  if constexpr (W) return __builtin_fmaf(w, term, acc);
+  else return acc + term;
+}
+
+// out[l] = {center, bbox, giou, depth, dim, angle} sums; comp[l] = sum |s - s*| / sum |s - s*| / s*   (W: every term times w_t)
+template <bool W>
+__global__ __launch_bounds__(256) void matched_fwd_kernel(const MatchedArgs a, const float *__restrict__ tw, float *__restrict__ out,
+                                                          float *__restrict__ comp) {
   __shared__ float scratch[4];
   const int l = blockIdx.x;
   float s_center = 0.f, s_bbox = 0.f, s_giou = 0.f, s_depth = 0.f, s_l1 = 0.f, s_dl = 0.f, s_angle = 0.f;
   for (int k = threadIdx.x; k < a.K; k += 256) {
     const Pair p = load_pair(a, l, k);
-    s_center += fabsf(p.box[0] - p.tbox[0]) + fabsf(p.box[1] - p.tbox[1]);
-    s_bbox += (fabsf(p.box[2] - p.tbox[2]) + fabsf(p.box[3] - p.tbox[3])) + (fabsf(p.box[4] - p.tbox[4]) + fabsf(p.box[5] - p.tbox[5]));
+    float w = 1.f;
+    if constexpr (W) w = tw[p.t];
+    s_center = wacc<W>(w, fabsf(p.box[0] - p.tbox[0]) + fabsf(p.box[1] - p.tbox[1]), s_center);
+    s_bbox = wacc<W>(w, (fabsf(p.box[2] - p.tbox[2]) + fabsf(p.box[3] - p.tbox[3])) + (fabsf(p.box[4] - p.tbox[4]) + fabsf(p.box[5] - p.tbox[5])),
+                     s_bbox);
     float xa[4], xb[4], g[4];
     to_xyxy(p.box, xa);
     to_xyxy(p.tbox, xb);
-    s_giou += 1.f - giou_grad(xa, xb, g);
-    s_depth += 1.4142f * expf(-p.dep[1]) * fabsf(p.dep[0] - p.tdep) + p.dep[1];
+    s_giou = wacc<W>(w, 1.f - giou_grad(xa, xb, g), s_giou);
+    s_depth = wacc<W>(w, 1.4142f * expf(-p.dep[1]) * fabsf(p.dep[0] - p.tdep) + p.dep[1], s_depth);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const float d = fabsf(p.dim[i] - p.tdim[i]);
-      s_l1 += d;
-      s_dl += d / p.tdim[i];
+      s_l1 = wacc<W>(w, d, s_l1);
+      s_dl = wacc<W>(w, d / p.tdim[i], s_dl);
     }
     float mx = p.ang[0];
 #pragma unroll
@@ -111,7 +126,7 @@ __global__ __launch_bounds__(256) void matched_fwd_kernel(const MatchedArgs a, f
     float logit_t = 0.f, res_p = 0.f;
 #pragma unroll
     for (int i = 0; i < 12; ++i) { if (i == p.bin) { logit_t = p.ang[i]; res_p = p.ang[12 + i]; } }
-    s_angle += (logf(se) + mx - logit_t) + fabsf(res_p - p.tres);
+    s_angle = wacc<W>(w, (logf(se) + mx - logit_t) + fabsf(res_p - p.tres), s_angle);
   }
   const float c = block_sum(s_center, scratch), bb = block_sum(s_bbox, scratch), gi = block_sum(s_giou, scratch);
   const float dp = block_sum(s_depth, scratch), l1 = block_sum(s_l1, scratch), dl = block_sum(s_dl, scratch);
@@ -124,8 +139,13 @@ __global__ __launch_bounds__(256) void matched_fwd_kernel(const MatchedArgs a, f
 }
 
 // gradients of sum_l sum_j go[l][j] * out[l][j] scattered to the matched rows (the buffers are zero elsewhere; a
-// (layer, image, query) row is matched at most once, so plain stores)
-__global__ __launch_bounds__(256) void matched_bwd_kernel(const MatchedArgs a, const float *__restrict__ comp, const float *__restrict__ go,
+// (layer, image, query) row is matched at most once, so plain stores).  W: the loop below stays the unweighted one, statement for
+// statement, and every thread then multiplies the rows it has just stored by their pairs' w_t -- a weight of 1 leaves the sibling's
+// bytes, 0.5 halves them, 0 leaves zeros.  (Folding w_t into the loop's expressions lets the compiler vectorise and contract them
+// otherwise than in the unweighted instantiation: the last bits differ then.)
+template <bool W>
+__global__ __launch_bounds__(256) void matched_bwd_kernel(const MatchedArgs a, const float *__restrict__ tw, const float *__restrict__ comp,
+                                                          const float *__restrict__ go,
                                                           float *__restrict__ g_boxes, float *__restrict__ g_depth,
                                                           float *__restrict__ g_dims, float *__restrict__ g_angle) {
   const int l = blockIdx.x;
@@ -163,6 +183,18 @@ __global__ __launch_bounds__(256) void matched_bwd_kernel(const MatchedArgs a, c
     for (int i = 0; i < 12; ++i) {
       g_angle[p.row * 24 + i] = w_angle * (ex[i] * inv - (i == p.bin ? 1.f : 0.f));
       g_angle[p.row * 24 + 12 + i] = (i == p.bin) ? w_angle * sgn(p.ang[12 + i] - p.tres) : 0.f;
+    }
+  }
+  if constexpr (W) {
+    const long long stride = (long long)a.NL * a.K;
+    for (int k = threadIdx.x; k < a.K; k += 256) {          // the same k as above: a thread rereads its own stores
+      const long long *ip = a.idx + (long long)l * a.K + k;
+      const long long row = ((long long)l * a.B + ip[0]) * a.Q + ip[stride];
+      const float w = tw[ip[2 * stride]];
+      for (int i = 0; i < 6; ++i) g_boxes[row * 6 + i] *= w;
+      for (int i = 0; i < 2; ++i) g_depth[row * 2 + i] *= w;
+      for (int i = 0; i < 3; ++i) g_dims[row * 3 + i] *= w;
+      for (int i = 0; i < 24; ++i) g_angle[row * 24 + i] *= w;
     }
   }
 }
@@ -247,6 +279,10 @@ __global__ __launch_bounds__(256) void label_audit_kernel(const AuditArgs a, dou
 // workgroup per layer: the layer's matched (image, query) -> class map lives in LDS.
 constexpr int kFocalThreads = 1024;
 constexpr int kFocalMaxCells = 32768;                 // B * Q cells of the class map (bytes of LDS)
+// with per-label weights a cell also keeps the pair that claimed it (16 bits; its weight is tw[flat target of that pair]): 3 bytes of
+// LDS per cell, 48 KB at the reach below
+constexpr int kFocalWeightedMaxCells = 16384;
+constexpr unsigned short kFocalNoPair = 0xffff;
 
 struct FocalArgs {
   const float *logits;                // [NL, B, Q, C]
@@ -257,13 +293,25 @@ struct FocalArgs {
   float alpha, gamma;
 };
 
-__device__ __forceinline__ void focal_class_map(const FocalArgs &a, int l, unsigned char *cls) {
+template <bool W>
+__device__ __forceinline__ void focal_class_map(const FocalArgs &a, int l, unsigned char *cls, unsigned short *pair) {
   const int cells = a.B * a.Q;
-  for (int i = threadIdx.x; i < cells; i += kFocalThreads) cls[i] = (unsigned char)a.C;          // C = "no object"
+  for (int i = threadIdx.x; i < cells; i += kFocalThreads) {
+    cls[i] = (unsigned char)a.C;          // C = "no object"
+    if constexpr (W) pair[i] = kFocalNoPair;
+  }
   __syncthreads();
   const long long *bi = a.idx + (long long)l * a.K, *qi = a.idx + ((long long)a.NL + l) * a.K, *ti = a.idx + ((long long)2 * a.NL + l) * a.K;
-  for (int k = threadIdx.x; k < a.K; k += kFocalThreads) cls[bi[k] * a.Q + qi[k]] = (unsigned char)a.labels[ti[k]];
+  for (int k = threadIdx.x; k < a.K; k += kFocalThreads) {
+    cls[bi[k] * a.Q + qi[k]] = (unsigned char)a.labels[ti[k]];
+    if constexpr (W) pair[bi[k] * a.Q + qi[k]] = (unsigned short)k;
+  }
   __syncthreads();
+}
+
+// weight of a cell: its target's, 1 for a cell no pair claimed
+__device__ __forceinline__ float focal_cell_weight(const FocalArgs &a, int l, const float *__restrict__ tw, unsigned short k) {
+  return k == kFocalNoPair ? 1.f : tw[a.idx[((long long)2 * a.NL + l) * a.K + k]];
 }
 
 // focal term of one logit x against target t in {0, 1} and its derivative (alpha < 0: no alpha weighting)
@@ -286,23 +334,47 @@ __device__ __forceinline__ float focal_term(float x, bool t, float alpha, float 
   return w * mod * ce;
 }
 
-__global__ __launch_bounds__(kFocalThreads) void focal_fwd_kernel(const FocalArgs a, float *__restrict__ out) {
-  __shared__ unsigned char cls[kFocalMaxCells];
+// W: all C terms of a matched cell times the weight of its target; the two logging entries stay unweighted.  The unweighted forward
+// adds alpha_t * mod * ce as ONE fma((alpha_t * mod), ce, sum) (the compiler contracts the term's last product into the accumulation);
+// the weighted one spells that fma out with the cell's weight folded into the first factor, so a weight of 1 gives the same bytes and
+// a weight of 0 leaves the sum.  focal_factors: the two factors, focal_term's own expressions.
+__device__ __forceinline__ void focal_factors(float x, bool t, float alpha, float gamma, float &wmod, float &ce) {
+  const float lse = log1pf(expf(-fabsf(x)));
+  const float log_p = -(fmaxf(-x, 0.f) + lse), log_1p = -(fmaxf(x, 0.f) + lse);
+  const float p = 1.f / (1.f + expf(-x));
+  const float q = t ? 1.f - p : p;
+  ce = t ? -log_p : -log_1p;
+  const float w = alpha >= 0.f ? (t ? alpha : 1.f - alpha) : 1.f;
+  wmod = w * (gamma == 2.f ? q * q : powf(q, gamma));
+}
+
+template <bool W>
+__global__ __launch_bounds__(kFocalThreads) void focal_fwd_kernel(const FocalArgs a, const float *__restrict__ tw, float *__restrict__ out) {
+  __shared__ unsigned char cls[W ? kFocalWeightedMaxCells : kFocalMaxCells];
+  __shared__ unsigned short pair[W ? kFocalWeightedMaxCells : 1];
   __shared__ float red[kFocalThreads / 64];
   __shared__ int card[256], correct;
   const int l = blockIdx.x, cells = a.B * a.Q;
   if (threadIdx.x < 256) card[threadIdx.x] = 0;
   if (threadIdx.x == 0) correct = 0;
-  focal_class_map(a, l, cls);
+  focal_class_map<W>(a, l, cls, pair);
   const float *lg = a.logits + (long long)l * cells * a.C;
   float sum = 0.f;
   for (int i = threadIdx.x; i < cells; i += kFocalThreads) {
     const int t = cls[i];
+    float w = 1.f;
+    if constexpr (W) w = focal_cell_weight(a, l, tw, pair[i]);
     int best = 0;
     float bv = lg[(long long)i * a.C];
     for (int c = 0; c < a.C; ++c) {
       const float x = lg[(long long)i * a.C + c];
-      sum += focal_term(x, c == t, a.alpha, a.gamma, nullptr);
+      if constexpr (W) {
+        float wmod, ce;
+        focal_factors(x, c == t, a.alpha, a.gamma, wmod, ce);
+        sum = __builtin_fmaf(wmod * w, ce, sum);
+      } else {
+        sum += focal_term(x, c == t, a.alpha, a.gamma, nullptr);
+      }
       if (x > bv) { bv = x; best = c; }                 // first maximum, like torch.argmax
     }
     if (best != a.C - 1) atomicAdd(&card[i / a.Q], 1);
@@ -325,11 +397,14 @@ __global__ __launch_bounds__(kFocalThreads) void focal_fwd_kernel(const FocalArg
 }
 
 // grad_logits[l, b, q, c] = grad_out[l] * d focal / d logit     (grad_out: gradient of the per-layer focal SUM)
-__global__ __launch_bounds__(kFocalThreads) void focal_bwd_kernel(const FocalArgs a, const float *__restrict__ grad_out,
-                                                                  float *__restrict__ grad_logits) {
+// W: the unweighted loop, statement for statement, then the C gradients of every matched cell times the weight of its target (see
+// matched_bwd_kernel); the workgroup meets in between, a cell's gradients come from other threads.
+template <bool W>
+__global__ __launch_bounds__(kFocalThreads) void focal_bwd_kernel(const FocalArgs a, const float *__restrict__ tw,
+                                                                  const float *__restrict__ grad_out, float *__restrict__ grad_logits) {
   __shared__ unsigned char cls[kFocalMaxCells];
   const int l = blockIdx.x, cells = a.B * a.Q;
-  focal_class_map(a, l, cls);
+  focal_class_map<false>(a, l, cls, nullptr);
   const float *lg = a.logits + (long long)l * cells * a.C;
   float *gl = grad_logits + (long long)l * cells * a.C;
   const float g = grad_out[l];
@@ -338,6 +413,15 @@ __global__ __launch_bounds__(kFocalThreads) void focal_bwd_kernel(const FocalArg
     float d;
     (void)focal_term(lg[i], c == cls[cell], a.alpha, a.gamma, &d);
     gl[i] = g * d;
+  }
+  if constexpr (W) {
+    __syncthreads();
+    const long long *bi = a.idx + (long long)l * a.K, *qi = a.idx + ((long long)a.NL + l) * a.K, *ti = a.idx + ((long long)2 * a.NL + l) * a.K;
+    for (int k = threadIdx.x; k < a.K; k += kFocalThreads) {
+      const float w = tw[ti[k]];
+      float *row = gl + (bi[k] * a.Q + qi[k]) * a.C;
+      for (int c = 0; c < a.C; ++c) row[c] *= w;
+    }
   }
 }
 

@@ -1078,7 +1078,21 @@ int mono_matched_losses_fwd_f32(const float *boxes, const float *depth, const fl
   if (!boxes || !depth || !dims || !angle || !idx || !t_box || !t_depth || !t_size || !t_bin || !t_res || !out || !comp) return -1;
   if (NL <= 0 || B <= 0 || Q <= 0 || K <= 0) return -2;
   const mono::MatchedArgs a{boxes, depth, dims, angle, idx, t_box, t_depth, t_size, t_res, t_bin, NL, B, Q, K};
-  mono::matched_fwd_kernel<<<NL, 256, 0, (hipStream_t)stream_>>>(a, out, comp);
+  mono::matched_fwd_kernel<false><<<NL, 256, 0, (hipStream_t)stream_>>>(a, nullptr, out, comp);
+  return (int)hipGetLastError();
+}
+
+// The same with per-label weights t_weight [T] (float32, finite, >= 0): every pair of flat target t enters its layer's sums times
+// t_weight[t]; comp [NL] = sum w |s - s*| / sum w |s - s*| / s*.  All weights 1: the bytes of mono_matched_losses_fwd_f32.
+int mono_matched_losses_weighted_fwd_f32(const float *boxes, const float *depth, const float *dims, const float *angle,
+                                         const long long *idx, const float *t_box, const float *t_depth, const float *t_size,
+                                         const long long *t_bin, const float *t_res, const float *t_weight, float *out, float *comp,
+                                         int NL, int B, int Q, int K, void *stream_) {
+  if (!boxes || !depth || !dims || !angle || !idx || !t_box || !t_depth || !t_size || !t_bin || !t_res || !t_weight || !out || !comp)
+    return -1;
+  if (NL <= 0 || B <= 0 || Q <= 0 || K <= 0) return -2;
+  const mono::MatchedArgs a{boxes, depth, dims, angle, idx, t_box, t_depth, t_size, t_res, t_bin, NL, B, Q, K};
+  mono::matched_fwd_kernel<true><<<NL, 256, 0, (hipStream_t)stream_>>>(a, t_weight, out, comp);
   return (int)hipGetLastError();
 }
 
@@ -1093,7 +1107,21 @@ int mono_matched_losses_bwd_f32(const float *boxes, const float *depth, const fl
     return -1;
   if (NL <= 0 || B <= 0 || Q <= 0 || K <= 0) return -2;
   const mono::MatchedArgs a{boxes, depth, dims, angle, idx, t_box, t_depth, t_size, t_res, t_bin, NL, B, Q, K};
-  mono::matched_bwd_kernel<<<NL, 256, 0, (hipStream_t)stream_>>>(a, comp, grad_out, g_boxes, g_depth, g_dims, g_angle);
+  mono::matched_bwd_kernel<false><<<NL, 256, 0, (hipStream_t)stream_>>>(a, nullptr, comp, grad_out, g_boxes, g_depth, g_dims, g_angle);
+  return (int)hipGetLastError();
+}
+
+int mono_matched_losses_weighted_bwd_f32(const float *boxes, const float *depth, const float *dims, const float *angle,
+                                         const long long *idx, const float *t_box, const float *t_depth, const float *t_size,
+                                         const long long *t_bin, const float *t_res, const float *t_weight, const float *comp,
+                                         const float *grad_out, float *g_boxes, float *g_depth, float *g_dims, float *g_angle, int NL,
+                                         int B, int Q, int K, void *stream_) {
+  if (!boxes || !depth || !dims || !angle || !idx || !t_box || !t_depth || !t_size || !t_bin || !t_res || !t_weight || !comp ||
+      !grad_out || !g_boxes || !g_depth || !g_dims || !g_angle)
+    return -1;
+  if (NL <= 0 || B <= 0 || Q <= 0 || K <= 0) return -2;
+  const mono::MatchedArgs a{boxes, depth, dims, angle, idx, t_box, t_depth, t_size, t_res, t_bin, NL, B, Q, K};
+  mono::matched_bwd_kernel<true><<<NL, 256, 0, (hipStream_t)stream_>>>(a, t_weight, comp, grad_out, g_boxes, g_depth, g_dims, g_angle);
   return (int)hipGetLastError();
 }
 
@@ -1423,7 +1451,22 @@ int mono_ddn_loss_fwd_f32(const float *logits, const float *boxes, const float *
   if (!logits || !boxes || !depth || !valid || !partial) return -1;
   if (B <= 0 || C <= 1 || H <= 0 || W <= 0 || N <= 0) return -2;
   const mono::DdnParams p = ddn_params(B, C, H, W, N, sb, sc, sp, alpha, gamma, fg_weight, bg_weight, depth_min, depth_max);
-  mono::ddn_loss_fwd_kernel<<<mono_ddn_loss_blocks(B, H, W), 256, 0, (hipStream_t)stream>>>(logits, boxes, depth, valid, partial, p);
+  mono::ddn_loss_fwd_kernel<false><<<mono_ddn_loss_blocks(B, H, W), 256, 0, (hipStream_t)stream>>>(logits, boxes, depth, valid, nullptr,
+                                                                                                  partial, p);
+  return (int)hipGetLastError();
+}
+
+// The same with per-box weights box_weight [B, N] (padded like depth; float32, finite, >= 0): a foreground pixel weighs
+// fg_weight * box_weight of the lowest slot among its covering boxes of the nearest depth.  All weights 1: the bytes of the above.
+int mono_ddn_loss_weighted_fwd_f32(const float *logits, const float *boxes, const float *depth, const unsigned char *valid,
+                                   const float *box_weight, float *partial, int B, int C, int H, int W, int N, long long sb,
+                                   long long sc, long long sp, float alpha, float gamma, float fg_weight, float bg_weight,
+                                   float depth_min, float depth_max, void *stream) {
+  if (!logits || !boxes || !depth || !valid || !box_weight || !partial) return -1;
+  if (B <= 0 || C <= 1 || H <= 0 || W <= 0 || N <= 0) return -2;
+  const mono::DdnParams p = ddn_params(B, C, H, W, N, sb, sc, sp, alpha, gamma, fg_weight, bg_weight, depth_min, depth_max);
+  mono::ddn_loss_fwd_kernel<true><<<mono_ddn_loss_blocks(B, H, W), 256, 0, (hipStream_t)stream>>>(logits, boxes, depth, valid, box_weight,
+                                                                                                 partial, p);
   return (int)hipGetLastError();
 }
 
@@ -1434,8 +1477,20 @@ int mono_ddn_loss_bwd_f32(const float *logits, const float *boxes, const float *
   if (!logits || !boxes || !depth || !valid || !grad_total || !grad_logits) return -1;
   if (B <= 0 || C <= 1 || H <= 0 || W <= 0 || N <= 0) return -2;
   const mono::DdnParams p = ddn_params(B, C, H, W, N, sb, sc, sp, alpha, gamma, fg_weight, bg_weight, depth_min, depth_max);
-  mono::ddn_loss_bwd_kernel<<<mono_ddn_loss_blocks(B, H, W), 256, 0, (hipStream_t)stream>>>(logits, boxes, depth, valid, grad_total,
-                                                                                           grad_logits, p);
+  mono::ddn_loss_bwd_kernel<false><<<mono_ddn_loss_blocks(B, H, W), 256, 0, (hipStream_t)stream>>>(logits, boxes, depth, valid, nullptr,
+                                                                                                  grad_total, grad_logits, p);
+  return (int)hipGetLastError();
+}
+
+int mono_ddn_loss_weighted_bwd_f32(const float *logits, const float *boxes, const float *depth, const unsigned char *valid,
+                                   const float *box_weight, const float *grad_total, float *grad_logits, int B, int C, int H, int W,
+                                   int N, long long sb, long long sc, long long sp, float alpha, float gamma, float fg_weight,
+                                   float bg_weight, float depth_min, float depth_max, void *stream) {
+  if (!logits || !boxes || !depth || !valid || !box_weight || !grad_total || !grad_logits) return -1;
+  if (B <= 0 || C <= 1 || H <= 0 || W <= 0 || N <= 0) return -2;
+  const mono::DdnParams p = ddn_params(B, C, H, W, N, sb, sc, sp, alpha, gamma, fg_weight, bg_weight, depth_min, depth_max);
+  mono::ddn_loss_bwd_kernel<true><<<mono_ddn_loss_blocks(B, H, W), 256, 0, (hipStream_t)stream>>>(logits, boxes, depth, valid, box_weight,
+                                                                                                 grad_total, grad_logits, p);
   return (int)hipGetLastError();
 }
 
@@ -1467,7 +1522,23 @@ int mono_focal_fwd_f32(const float *logits, const long long *idx, const long lon
   if (!logits || !out || !sizes || (K > 0 && (!idx || !labels))) return -1;
   if (NL <= 0 || B <= 0 || Q <= 0 || C <= 0 || C > 255 || K < 0 || B > 256 || (long long)B * Q > mono::kFocalMaxCells) return -2;
   const mono::FocalArgs a{logits, idx, labels, sizes, NL, B, Q, C, K, alpha, gamma};
-  mono::focal_fwd_kernel<<<NL, mono::kFocalThreads, 0, (hipStream_t)stream>>>(a, out);
+  mono::focal_fwd_kernel<false><<<NL, mono::kFocalThreads, 0, (hipStream_t)stream>>>(a, nullptr, out);
+  return (int)hipGetLastError();
+}
+
+// The same with per-label weights t_weight [T]: all C terms of a matched cell times the weight of its target, unmatched cells as they
+// are; class and cardinality errors unweighted.  Reach: B * Q <= mono_focal_weighted_max_cells() (a cell also keeps its pair in LDS).
+int mono_focal_weighted_max_cells(void) { return mono::kFocalWeightedMaxCells; }
+
+int mono_focal_weighted_fwd_f32(const float *logits, const long long *idx, const long long *labels, const float *sizes,
+                                const float *t_weight, float *out, int NL, int B, int Q, int C, int K, float alpha, float gamma,
+                                void *stream) {
+  if (!logits || !out || !sizes || (K > 0 && (!idx || !labels || !t_weight))) return -1;
+  if (NL <= 0 || B <= 0 || Q <= 0 || C <= 0 || C > 255 || K < 0 || B > 256 || (long long)B * Q > mono::kFocalWeightedMaxCells ||
+      K >= (int)mono::kFocalNoPair)
+    return -2;
+  const mono::FocalArgs a{logits, idx, labels, sizes, NL, B, Q, C, K, alpha, gamma};
+  mono::focal_fwd_kernel<true><<<NL, mono::kFocalThreads, 0, (hipStream_t)stream>>>(a, t_weight, out);
   return (int)hipGetLastError();
 }
 
@@ -1476,7 +1547,19 @@ int mono_focal_bwd_f32(const float *logits, const long long *idx, const long lon
   if (!logits || !grad_out || !grad_logits || (K > 0 && (!idx || !labels))) return -1;
   if (NL <= 0 || B <= 0 || Q <= 0 || C <= 0 || C > 255 || K < 0 || (long long)B * Q > mono::kFocalMaxCells) return -2;
   const mono::FocalArgs a{logits, idx, labels, nullptr, NL, B, Q, C, K, alpha, gamma};
-  mono::focal_bwd_kernel<<<NL, mono::kFocalThreads, 0, (hipStream_t)stream>>>(a, grad_out, grad_logits);
+  mono::focal_bwd_kernel<false><<<NL, mono::kFocalThreads, 0, (hipStream_t)stream>>>(a, nullptr, grad_out, grad_logits);
+  return (int)hipGetLastError();
+}
+
+int mono_focal_weighted_bwd_f32(const float *logits, const long long *idx, const long long *labels, const float *t_weight,
+                                const float *grad_out, float *grad_logits, int NL, int B, int Q, int C, int K, float alpha, float gamma,
+                                void *stream) {
+  if (!logits || !grad_out || !grad_logits || (K > 0 && (!idx || !labels || !t_weight))) return -1;
+  if (NL <= 0 || B <= 0 || Q <= 0 || C <= 0 || C > 255 || K < 0 || (long long)B * Q > mono::kFocalWeightedMaxCells ||
+      K >= (int)mono::kFocalNoPair)
+    return -2;
+  const mono::FocalArgs a{logits, idx, labels, nullptr, NL, B, Q, C, K, alpha, gamma};
+  mono::focal_bwd_kernel<true><<<NL, mono::kFocalThreads, 0, (hipStream_t)stream>>>(a, t_weight, grad_out, grad_logits);
   return (int)hipGetLastError();
 }
 

@@ -45,7 +45,7 @@ import tqdm
 from ..image_prep import is_raw_batch, prepare
 from ..monodetr import misc
 from ..monodetr.criterion import weighted_total
-from ..synthetic import attach_host_mask
+from ..synthetic import attach_host_mask, attach_host_weight, host_label_weight
 from ..synthetic import prepare_targets as _prepare_targets
 from .save_helper import get_checkpoint_state, load_checkpoint, save_checkpoint, unwrap
 
@@ -92,9 +92,12 @@ def stage_batch(raw, device):
             inputs = inputs.contiguous(memory_format=torch.channels_last)
     calibs = calibs.to(device, non_blocking=True)
     host_mask = targets["mask_2d"].numpy() if not targets["mask_2d"].is_cuda else None
+    host_weight = targets["label_weight"].numpy() if "label_weight" in targets and not targets["label_weight"].is_cuda else None
     targets = {k: v.to(device, non_blocking=True) for k, v in targets.items()}
     if host_mask is not None:
         attach_host_mask(targets["mask_2d"], host_mask)      # prepare_targets then needs no device sync
+    if host_weight is not None:
+        attach_host_weight(targets["label_weight"], host_weight)      # nor does the weighted normaliser
     return inputs, calibs, targets, info
 
 
@@ -365,7 +368,8 @@ class Trainer(object):
 
     @staticmethod
     def _host_box_count(raw):
-        """Boxes of one collated loader batch, from the object mask on the host (no device synchronisation)."""
+        """Boxes of one collated loader batch, from the object mask on the host (no device synchronisation); with ``label_weight`` in
+        the targets the sum of the boxes' weights (a float)."""
         mask = raw[2]["mask_2d"]
         host = getattr(mask, "_host_mask", None)
         if host is None:
@@ -373,6 +377,9 @@ class Trainer(object):
                 raise ValueError("gradient accumulation counts the boxes of a cycle on the host: a device-resident batch needs "
                                  "synthetic.attach_host_mask on its mask_2d")
             host = mask.numpy()
+        if "label_weight" in raw[2]:               # dataset.label_weights: the boxes count with their weights
+            from ..monodetr.criterion import label_weight_sum
+            return label_weight_sum(host_label_weight(raw[2]), host)
         return int(np.count_nonzero(host))
 
     def _cycle_num_boxes(self, n_boxes, micro_steps):

@@ -17,6 +17,9 @@ checkpoints/best_kitti_k360_to_kitti/monodetr_kk360_05.yaml:18): monosowa_amd/ph
 draws); the same draws are consumed from `np.random`, every other output is identical, and monosowa_amd/image_prep.py turns
 a batch of them into the same float32 images with one HIP launch.
 
+`label_weights` (optional, training splits only; this project's): a weight per label, `targets["label_weight"]` float32 `[50]`, from
+the label file's score column or from a CSV of `(img_id, line, weight)` -- see `KITTI_Dataset.__init__`.
+
 Not carried over (off in both shipped configs and tied to files of the pseudo-label pipeline): `use_add_data` (per-car
 masks / lidar in dill+zstd), `use_depth`, `output_lidar` -- they raise.
 """
@@ -58,6 +61,7 @@ class Object3d:
         self.dis_to_cam = np.linalg.norm(self.pos)
         self.ry = float(f[14])
         self.score = float(f[15]) if len(f) == 16 else -1.0
+        self.has_score = len(f) == 16
         height = float(self.box2d[3]) - float(self.box2d[1]) + 1
         if self.trucation == -1:
             self.level_str, self.level = "DontCare", 0
@@ -74,6 +78,46 @@ class Object3d:
 def get_objects_from_label(label_file):
     with open(label_file, "r") as f:
         return [Object3d(line) for line in f.readlines()]
+
+
+def _check_label_weight(value, where):
+    """A per-label weight: finite and not negative (it may exceed 1); anything else is refused, naming where it stands."""
+    try:
+        w = float(value)
+    except (TypeError, ValueError):
+        raise ValueError("%s: %r is not a number" % (where, value)) from None
+    if not np.isfinite(w) or w < 0:
+        raise ValueError("%s: a label weight must be finite and not negative, got %r" % (where, value))
+    return w
+
+
+def read_label_weights(path):
+    """{(img_id, line): weight} of a label-weight CSV (header ``img_id,line,weight``; ``line`` the object's index in its label file --
+    the identity tools/label_audit.py writes).  A missing file, another header, a duplicate (img_id, line), a negative or non-finite
+    weight: ValueError naming the file (and the line)."""
+    import csv
+    if not os.path.isfile(path):
+        raise ValueError("dataset.label_weights: %s does not exist" % path)
+    table = {}
+    with open(path, newline="") as f:
+        rows = csv.reader(f)
+        header = next(rows, None)
+        if header is None or [h.strip() for h in header] != ["img_id", "line", "weight"]:
+            raise ValueError("dataset.label_weights: %s: the header must be img_id,line,weight, got %r" % (path, header))
+        for n, row in enumerate(rows, start=2):
+            if not row:
+                continue
+            where = "dataset.label_weights: %s line %d" % (path, n)
+            if len(row) != 3:
+                raise ValueError("%s: expected img_id,line,weight, got %r" % (where, row))
+            try:
+                key = (int(row[0]), int(row[1]))
+            except ValueError:
+                raise ValueError("%s: img_id and line must be integers, got %r" % (where, row[:2])) from None
+            if key in table:
+                raise ValueError("%s: (img_id, line) = %r is listed twice" % (where, key))
+            table[key] = _check_label_weight(row[2], where)
+    return table
 
 
 def get_calib_from_file(calib_file):
@@ -174,6 +218,8 @@ def affine_transform(pt, t):
 
 
 class KITTI_Dataset(data.Dataset):
+    label_weights = None             # dataset.label_weights: None, 'score' or {(img_id, line): weight}
+
     def __init__(self, split, cfg):
         self.root_dir = cfg.get("root_dir")
         self.split = split
@@ -186,6 +232,16 @@ class KITTI_Dataset(data.Dataset):
         self.calib_dir = os.path.join(self.data_dir, "calib")
         self.label_dir = os.path.join(self.data_dir, "label_2")
         self.data_augmentation = split in ["train", "trainval"]
+        # dataset.label_weights (optional; training splits only): None -- the targets are what they were; 'score' -- a label's weight
+        # is the 16th column of its line; any other string -- a CSV of (img_id, line, weight), read_label_weights.  Labels without
+        # a weight of their own get dataset.label_weight_default.
+        self.label_weights = None
+        source = cfg.get("label_weights") if self.data_augmentation else None
+        if source is not None:
+            if not isinstance(source, str):
+                raise ValueError("dataset.label_weights = %r is neither 'score' nor the path of a CSV file (absent or None: off)" % (source,))
+            self.label_weight_default = _check_label_weight(cfg.get("label_weight_default", 1.0), "dataset.label_weight_default")
+            self.label_weights = "score" if source == "score" else read_label_weights(source)
 
     @classmethod
     def settings(cls, cfg):
@@ -337,6 +393,16 @@ class KITTI_Dataset(data.Dataset):
         boxes = np.zeros((n, 4), dtype=np.float32)
         boxes_3d = np.zeros((n, 6), dtype=np.float32)
         objects_out = np.zeros((n, 7), dtype=np.float32)
+        label_weight = None
+        if self.label_weights is not None:         # slot i is line i of the label file, whatever the flip and the crop did
+            label_weight = np.full((n,), self.label_weight_default, dtype=np.float32)
+            for i in range(min(len(objects), n)):
+                if self.label_weights == "score":
+                    if objects[i].has_score:
+                        label_weight[i] = _check_label_weight(objects[i].score, "dataset.label_weights = 'score': %s line %d"
+                                                              % (os.path.join(self.label_dir, "%06d.txt" % index), i + 1))
+                elif (index, i) in self.label_weights:
+                    label_weight[i] = self.label_weights[(index, i)]
         for i in range(min(len(objects), n)):
             o = objects[i]
             if o.cls_type not in self.writelist or o.level_str == "UnKnown" or o.pos[-1] < 2 or o.pos[-1] > 65:
@@ -383,6 +449,8 @@ class KITTI_Dataset(data.Dataset):
         targets = {"calibs": calibs, "indices": indices, "img_size": img_size, "labels": labels, "boxes": boxes, "boxes_3d": boxes_3d,
                    "depth": depth, "size_2d": size_2d, "size_3d": size_3d, "src_size_3d": src_size_3d, "heading_bin": heading_bin,
                    "heading_res": heading_res, "mask_2d": mask_2d, "objects": objects_out}
+        if label_weight is not None:
+            targets["label_weight"] = label_weight
         info.update({"affine": trans, "affine_inv": trans_inv, "scale_depth": crop_scale, "calib_P2": calib.P2, "calib_R0": calib.R0,
                      "calib_V2C": calib.V2C, "resolution": self.resolution, "flip": flipped,
                      "templates_dimensions": np.array([self.template_height, self.template_width, self.template_length], dtype=np.float32)})

@@ -20,7 +20,8 @@ from torch import nn
 from . import box_ops
 from .losses import DDNLoss, sigmoid_focal_loss
 from .misc import accuracy, get_world_size, is_dist_avail_and_initialized
-from ..pointwise import focal_classification, focal_classification_supported, matched_losses, matched_losses_supported
+from ..pointwise import (focal_classification, focal_classification_supported, focal_classification_weighted_supported, matched_losses,
+                         matched_losses_supported)
 
 
 def _paired_giou(a, b):
@@ -40,6 +41,32 @@ def _dev(values, dtype, device):
     ``torch.as_tensor(list, device=cuda)`` wait for every queued kernel (214 ms behind a 214 ms queue,
     tools/h2d_probe.py), a staged ``.to(device, non_blocking=True)`` of a CPU tensor returns in 70 us."""
     return torch.as_tensor(np.asarray(values)).to(dtype).to(device, non_blocking=True)
+
+
+def label_weight_sum(weights, mask=None):
+    """W of the weighted normaliser: the per-label weights (host values; with ``mask`` the padded [B, max_objs] array and its object
+    mask) added up in float64 in flat order."""
+    w = np.asarray(weights, dtype=np.float64)
+    w = w[np.asarray(mask, dtype=bool)] if mask is not None else w.reshape(-1)
+    return float(np.cumsum(w)[-1]) if w.size else 0.0
+
+
+def _has_label_weight(targets):
+    flat = getattr(targets, "flat", None)
+    if flat is not None:
+        return "label_weight" in flat
+    return len(targets) > 0 and all("label_weight" in t for t in targets)
+
+
+def _host_weight_sum(targets):
+    """``TargetList.weight_sum`` where ``prepare_targets`` formed it, else from host-resident weights; never a device read."""
+    ws = getattr(targets, "weight_sum", None)
+    if ws is not None:
+        return float(ws)
+    if any(t["label_weight"].is_cuda for t in targets):
+        raise ValueError("the weighted normaliser is formed on the host: device-resident label_weight needs the weight_sum that "
+                         "synthetic.prepare_targets sets from the host copy (synthetic.attach_host_weight)")
+    return label_weight_sum(np.concatenate([t["label_weight"].detach().reshape(-1).numpy() for t in targets]))
 
 
 FUSED_FOCAL = True       # classification side (focal sums, class / cardinality errors) as one HIP kernel each way
@@ -201,8 +228,14 @@ class SetCriterion(nn.Module):
         onehot = torch.zeros([src_logits.shape[0], src_logits.shape[1], src_logits.shape[2] + 1],
                              dtype=src_logits.dtype, device=src_logits.device)
         onehot.scatter_(2, target_classes.unsqueeze(-1), 1)
-        loss_ce = sigmoid_focal_loss(src_logits, onehot[:, :, :-1], num_boxes, alpha=self.focal_alpha, gamma=2) \
-            * src_logits.shape[1]
+        if _has_label_weight(targets):              # the C terms of a matched query times its label's weight, 1 elsewhere
+            cell_w = torch.ones(src_logits.shape[:2], dtype=src_logits.dtype, device=src_logits.device)
+            cell_w[idx] = self._matched(targets, indices, "label_weight").to(src_logits.dtype)
+            loss_ce = sigmoid_focal_loss(src_logits, onehot[:, :, :-1], num_boxes, alpha=self.focal_alpha, gamma=2,
+                                         weight=cell_w.unsqueeze(-1)) * src_logits.shape[1]
+        else:
+            loss_ce = sigmoid_focal_loss(src_logits, onehot[:, :, :-1], num_boxes, alpha=self.focal_alpha, gamma=2) \
+                * src_logits.shape[1]
         losses = {"loss_ce": loss_ce}
         if log:
             losses["class_error"] = 100 - accuracy(src_logits[idx], target_classes_o)[0]
@@ -219,18 +252,23 @@ class SetCriterion(nn.Module):
         idx = self._get_src_permutation_idx(indices)
         src = outputs["pred_boxes"][:, :, 0:2][idx]
         tgt = self._matched(targets, indices, "boxes_3d", slice(0, 2))
+        if _has_label_weight(targets):
+            w = self._matched(targets, indices, "label_weight").to(src.dtype)
+            return {"loss_center": (F.l1_loss(src, tgt, reduction="none") * w[:, None]).sum() / num_boxes}
         return {"loss_center": F.l1_loss(src, tgt, reduction="none").sum() / num_boxes}
 
     def loss_boxes(self, outputs, targets, indices, num_boxes, info=None):
         idx = self._get_src_permutation_idx(indices)
         src_lrtb = outputs["pred_boxes"][:, :, 2:6][idx]
         tgt_lrtb = self._matched(targets, indices, "boxes_3d", slice(2, 6))
-        losses = {"loss_bbox": F.l1_loss(src_lrtb, tgt_lrtb, reduction="none").sum() / num_boxes}
+        w = self._matched(targets, indices, "label_weight").to(src_lrtb.dtype) if _has_label_weight(targets) else None
+        l1 = F.l1_loss(src_lrtb, tgt_lrtb, reduction="none")
+        losses = {"loss_bbox": (l1 if w is None else l1 * w[:, None]).sum() / num_boxes}
         src_boxes = outputs["pred_boxes"][idx]
         tgt_boxes = self._matched(targets, indices, "boxes_3d")
         giou = torch.diag(box_ops.generalized_box_iou(box_ops.box_cxcylrtb_to_xyxy(src_boxes),
                                                       box_ops.box_cxcylrtb_to_xyxy(tgt_boxes), check=False))
-        losses["loss_giou"] = (1 - giou).sum() / num_boxes
+        losses["loss_giou"] = ((1 - giou) if w is None else (1 - giou) * w).sum() / num_boxes
         return losses
 
     def loss_depths(self, outputs, targets, indices, num_boxes, info=None):
@@ -239,6 +277,8 @@ class SetCriterion(nn.Module):
         tgt = self._matched(targets, indices, "depth").squeeze()
         depth, log_var = src[:, 0], src[:, 1]
         loss = 1.4142 * torch.exp(-log_var) * torch.abs(depth - tgt) + log_var     # Laplacian aleatoric
+        if _has_label_weight(targets):
+            loss = loss * self._matched(targets, indices, "label_weight").to(loss.dtype)
         return {"loss_depth": loss.sum() / num_boxes}
 
     def loss_dims(self, outputs, targets, indices, num_boxes, info=None):
@@ -246,6 +286,12 @@ class SetCriterion(nn.Module):
         src = outputs["pred_3d_dim"][idx]
         tgt = self._matched(targets, indices, "size_3d")
         dim_loss = torch.abs(src - tgt) / tgt.clone().detach()
+        if _has_label_weight(targets):              # sum w |s - s*| / sum w |s - s*| / s*, as two means over the same count
+            w = self._matched(targets, indices, "label_weight").to(src.dtype)[:, None]
+            dim_loss = dim_loss * w
+            with torch.no_grad():
+                compensation = (torch.abs(src - tgt) * w).mean() / dim_loss.mean()
+            return {"loss_dim": (dim_loss * compensation).sum() / num_boxes}
         with torch.no_grad():
             compensation = F.l1_loss(src, tgt) / dim_loss.mean()
         return {"loss_dim": (dim_loss * compensation).sum() / num_boxes}
@@ -260,6 +306,8 @@ class SetCriterion(nn.Module):
             dim=1, index=cls_t.view(-1, 1), value=1)
         res_pred = torch.sum(heading[:, 12:24] * onehot, 1)
         reg_loss = F.l1_loss(res_pred, res_t, reduction="none")
+        if _has_label_weight(targets):
+            return {"loss_angle": ((cls_loss + reg_loss) * self._matched(targets, indices, "label_weight").to(cls_loss.dtype)).sum() / num_boxes}
         return {"loss_angle": (cls_loss + reg_loss).sum() / num_boxes}
 
     def loss_depth_map(self, outputs, targets, indices, num_boxes, info=None):
@@ -269,6 +317,9 @@ class SetCriterion(nn.Module):
         scale = torch.tensor([w, h, w, h], device=logits.device, dtype=logits.dtype)
         boxes = box_ops.box_cxcywh_to_xyxy(torch.cat([t["boxes"] for t in targets], dim=0) * scale)
         centre_depth = torch.cat([t["depth"] for t in targets], dim=0).squeeze(dim=1)
+        if _has_label_weight(targets):
+            return {"loss_depth_map": self.ddn_loss(logits, boxes, num_gt_per_img, centre_depth,
+                                                    box_weight=torch.cat([t["label_weight"] for t in targets], dim=0))}
         return {"loss_depth_map": self.ddn_loss(logits, boxes, num_gt_per_img, centre_depth)}
 
     def loss_tfl(self, outputs, targets, indices, num_boxes, info=None):
@@ -292,7 +343,11 @@ class SetCriterion(nn.Module):
 
     # ------------------------------------------------------------------ batched formulation
     def _num_boxes(self, targets, group_num, device):
-        n = float(sum(len(t["labels"]) for t in targets) * group_num)
+        """max(n * group_num / ranks, 1), n the label count -- with ``label_weight`` in the targets the sum of the weights."""
+        if _has_label_weight(targets):
+            n = float(_host_weight_sum(targets) * group_num)
+        else:
+            n = float(sum(len(t["labels"]) for t in targets) * group_num)
         if is_dist_avail_and_initialized():       # stays on the device: dividing by a tensor needs no sync
             t = _dev([n], torch.float, device)
             torch.distributed.all_reduce(t)
@@ -317,8 +372,11 @@ class SetCriterion(nn.Module):
         T = sum(sizes)
         flat_keys = ("labels", "boxes_3d", "boxes", "depth", "size_3d", "heading_bin", "heading_res")
         flat = getattr(targets, "flat", None)              # prepare_targets hands the batch-flat tensors along (7 launches fewer)
+        weighted = _has_label_weight(targets)
         if flat is None or any(k not in flat for k in flat_keys) or flat["labels"].shape[0] != T:
-            flat = {k: torch.cat([t[k] for t in targets], dim=0) for k in flat_keys}
+            flat = {k: torch.cat([t[k] for t in targets], dim=0) for k in flat_keys + (("label_weight",) if weighted else ())}
+        # per-label weights [T] (float32, finite, >= 0): every loss term a label feeds times its weight; None: nothing below changes
+        t_weight = flat["label_weight"].reshape(-1) if weighted else None
         if num_boxes is None:
             num_boxes = self._num_boxes(targets, group_num, dev)
 
@@ -342,7 +400,11 @@ class SetCriterion(nn.Module):
             valid_t = torch.zeros((B, 1), dtype=torch.bool, device=dev)
             boxes2d = torch.zeros((B, 1, 4), device=dev, dtype=logits.dtype)
             depth2d = torch.zeros((B, 1), device=dev, dtype=logits.dtype)
-        loss_depth_map = self.ddn_loss.forward_padded(outputs["pred_depth_map_logits"], boxes2d, depth2d, valid_t)
+        if weighted:
+            weight2d = t_weight.to(logits.dtype)[slot_t] if maxn else torch.ones((B, 1), device=dev, dtype=logits.dtype)
+            loss_depth_map = self.ddn_loss.forward_padded(outputs["pred_depth_map_logits"], boxes2d, depth2d, valid_t, box_weight=weight2d)
+        else:
+            loss_depth_map = self.ddn_loss.forward_padded(outputs["pred_depth_map_logits"], boxes2d, depth2d, valid_t)
 
         # everything the fused tail needs that does not depend on the assignment is made ready BEFORE the wait: behind it the
         # GPU queue is empty and every microsecond of host time is step time (measured: 1.05 ms from indices to total)
@@ -353,6 +415,7 @@ class SetCriterion(nn.Module):
             prep_t = [flat["boxes_3d"].to(f32).contiguous(), flat["depth"].reshape(-1).to(f32).contiguous(), flat["size_3d"].to(f32).contiguous(),
                       flat["heading_bin"].reshape(-1).to(i64).contiguous(), flat["heading_res"].reshape(-1).to(f32).contiguous()]
             labels64 = flat["labels"].to(i64).contiguous()
+            weight32 = t_weight.to(f32).contiguous() if weighted else None
             sizes_dev = _dev(sizes, f32, dev)
             nb = num_boxes if torch.is_tensor(num_boxes) else float(num_boxes)
             # rows of the loss matrix: focal sum, class error, cardinality error, six matched-pair sums; divided by num_boxes
@@ -370,7 +433,16 @@ class SetCriterion(nn.Module):
             with torch.no_grad():
                 self.audit.observe(*[t.detach() for t in (prep if fused_tail else (logits, boxes, depth, dims, angle))], idx,
                                    dict(flat, labels=labels64) if fused_tail else flat, layer=0)
-        if fused_tail and K > 0 and focal_classification_supported(logits, idx):
+        if weighted and fused_tail and K > 0 and focal_classification_weighted_supported(logits, idx):
+            # the same four launches through the weighted entry points
+            from ..pointwise import _FocalClassificationWeighted, _MatchedLossesWeighted
+            cls3 = _FocalClassificationWeighted.apply(prep[0], idx, labels64, sizes_dev, weight32, float(self.focal_alpha), 2.0)
+            sums = _MatchedLossesWeighted.apply(prep[1], prep[2], prep[3], prep[4], idx, *prep_t, weight32)
+            mat = torch.cat([cls3, sums], 1).t() * scale_col                     # [9, NL]
+            keys = ("loss_ce", "class_error", "cardinality_error", "loss_center", "loss_bbox", "loss_giou", "loss_depth", "loss_dim",
+                    "loss_angle")
+            return self._finish(keys, NL, dev, loss_depth_map, mat=mat)
+        if not weighted and fused_tail and K > 0 and focal_classification_supported(logits, idx):
             # the whole criterion behind the matching in four launches: classification side + matched-pair losses, forward
             # and backward (csrc/matched_losses.hip), the loss matrix in two more
             from ..pointwise import _FocalClassification, _MatchedLosses
@@ -396,6 +468,12 @@ class SetCriterion(nn.Module):
         focal = ce * ((1 - p_t) ** 2)
         if self.focal_alpha >= 0:
             focal = (self.focal_alpha * onehot + (1 - self.focal_alpha) * (1 - onehot)) * focal
+        pair_w = None
+        if weighted:                                # [NL, K] weight of every pair; a matched cell carries its target's, the others 1
+            pair_w = t_weight.to(logits.dtype)[t_idx] if T else torch.zeros((NL, 0), dtype=logits.dtype, device=dev)
+            cell_w = torch.ones((NL, B, Q), dtype=logits.dtype, device=dev)
+            cell_w[l_idx, b_idx, q_idx] = pair_w
+            focal = focal * cell_w.unsqueeze(-1)
         per_layer["loss_ce"] = focal.mean(2).sum((1, 2)) / num_boxes * Q
         matched_logits = take(logits)
         if K:
@@ -410,23 +488,28 @@ class SetCriterion(nn.Module):
 
         if FUSED_MATCHED and matched_losses_supported(boxes, idx):
             # all six matched-pair losses of all layers: one HIP launch forward, one backward (csrc/matched_losses.hip)
-            sums = matched_losses(boxes, depth, dims, angle, idx, flat["boxes_3d"], flat["depth"], flat["size_3d"],
-                                  flat["heading_bin"], flat["heading_res"]) / num_boxes
+            if weighted:
+                sums = matched_losses(boxes, depth, dims, angle, idx, flat["boxes_3d"], flat["depth"], flat["size_3d"],
+                                      flat["heading_bin"], flat["heading_res"], weight=t_weight) / num_boxes
+            else:
+                sums = matched_losses(boxes, depth, dims, angle, idx, flat["boxes_3d"], flat["depth"], flat["size_3d"],
+                                      flat["heading_bin"], flat["heading_res"]) / num_boxes
             for j, k in enumerate(("loss_center", "loss_bbox", "loss_giou", "loss_depth", "loss_dim", "loss_angle")):
                 per_layer[k] = sums[:, j]
             return self._finish(per_layer, NL, dev, loss_depth_map)
         # boxes: 3D-centre L1, l/r/t/b L1, GIoU of matched pairs
+        wk = (lambda x: x) if pair_w is None else (lambda x: x * (pair_w if x.dim() == 2 else pair_w.unsqueeze(-1)))   # a pair's terms x w_t
         src_box, tgt_box = take(boxes), flat["boxes_3d"][t_idx]
-        per_layer["loss_center"] = (src_box[..., 0:2] - tgt_box[..., 0:2]).abs().sum((1, 2)) / num_boxes
-        per_layer["loss_bbox"] = (src_box[..., 2:6] - tgt_box[..., 2:6]).abs().sum((1, 2)) / num_boxes
+        per_layer["loss_center"] = wk((src_box[..., 0:2] - tgt_box[..., 0:2]).abs()).sum((1, 2)) / num_boxes
+        per_layer["loss_bbox"] = wk((src_box[..., 2:6] - tgt_box[..., 2:6]).abs()).sum((1, 2)) / num_boxes
         giou = _paired_giou(box_ops.box_cxcylrtb_to_xyxy(src_box), box_ops.box_cxcylrtb_to_xyxy(tgt_box))
-        per_layer["loss_giou"] = (1 - giou).sum(1) / num_boxes
+        per_layer["loss_giou"] = wk(1 - giou).sum(1) / num_boxes
         # depth (Laplacian aleatoric uncertainty)
         src_d, tgt_d = take(depth), flat["depth"][t_idx].squeeze(-1)
-        per_layer["loss_depth"] = (1.4142 * torch.exp(-src_d[..., 1]) * (src_d[..., 0] - tgt_d).abs() + src_d[..., 1]).sum(1) / num_boxes
-        # 3D size (dimension-aware L1 with the per-layer compensation weight)
+        per_layer["loss_depth"] = wk(1.4142 * torch.exp(-src_d[..., 1]) * (src_d[..., 0] - tgt_d).abs() + src_d[..., 1]).sum(1) / num_boxes
+        # 3D size (dimension-aware L1 with the per-layer compensation weight; weighted: sum w |s - s*| / sum w |s - s*| / s*)
         src_s, tgt_s = take(dims), flat["size_3d"][t_idx]
-        l1 = (src_s - tgt_s).abs()
+        l1 = wk((src_s - tgt_s).abs())
         dim_loss = l1 / tgt_s.detach()
         with torch.no_grad():
             comp = l1.mean((1, 2)) / dim_loss.mean((1, 2))
@@ -437,7 +520,7 @@ class SetCriterion(nn.Module):
         res_t = flat["heading_res"][t_idx].view(NL, K)
         cls_loss = F.cross_entropy(heading[..., 0:12].reshape(NL * K, 12), cls_t.reshape(-1), reduction="none").view(NL, K)
         res_pred = torch.gather(heading[..., 12:24], 2, cls_t.unsqueeze(-1)).squeeze(-1)
-        per_layer["loss_angle"] = (cls_loss + (res_pred - res_t).abs()).sum(1) / num_boxes
+        per_layer["loss_angle"] = wk(cls_loss + (res_pred - res_t).abs()).sum(1) / num_boxes
 
         return self._finish(per_layer, NL, dev, loss_depth_map)
 
@@ -484,7 +567,10 @@ class SetCriterion(nn.Module):
             self._observe_layerwise(outputs_without_aux, targets, indices)
 
         if num_boxes is None:
-            num_boxes = sum(len(t["labels"]) for t in targets) * group_num
+            if _has_label_weight(targets):
+                num_boxes = _host_weight_sum(targets) * group_num
+            else:
+                num_boxes = sum(len(t["labels"]) for t in targets) * group_num
             num_boxes = torch.as_tensor([num_boxes], dtype=torch.float, device=next(iter(outputs.values())).device)
             if is_dist_avail_and_initialized():
                 torch.distributed.all_reduce(num_boxes)

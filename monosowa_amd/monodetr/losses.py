@@ -16,13 +16,16 @@ import torch.nn.functional as F
 from torch import nn
 
 
-def sigmoid_focal_loss(inputs, targets, num_boxes, alpha: float = 0.25, gamma: float = 2):
+def sigmoid_focal_loss(inputs, targets, num_boxes, alpha: float = 0.25, gamma: float = 2, weight=None):
+    """``weight`` (broadcast against ``inputs``, e.g. [B, Q, 1]): a factor per term, the per-label weights of the matched queries."""
     prob = inputs.sigmoid()
     ce = F.binary_cross_entropy_with_logits(inputs, targets, reduction="none")
     p_t = prob * targets + (1 - prob) * (1 - targets)
     loss = ce * ((1 - p_t) ** gamma)
     if alpha >= 0:
         loss = (alpha * targets + (1 - alpha) * (1 - targets)) * loss
+    if weight is not None:
+        loss = loss * weight
     return loss.mean(1).sum() / num_boxes
 
 
@@ -56,6 +59,19 @@ def _int_boxes(gt_boxes2d):
     return b.long()
 
 
+def _pad_per_image(flat, num_gt_per_img, fill=0):
+    """[sum n, ...] -> [B, max n, ...] padded with ``fill``, and the [B, max n] validity mask"""
+    B, N = len(num_gt_per_img), max(max(num_gt_per_img, default=0), 1)
+    out = flat.new_full((B, N) + tuple(flat.shape[1:]), fill)
+    valid = torch.zeros((B, N), dtype=torch.bool, device=flat.device)
+    start = 0
+    for b, n in enumerate(num_gt_per_img):
+        out[b, :n] = flat[start:start + n]
+        valid[b, :n] = True
+        start += n
+    return out, valid
+
+
 class DDNLoss(nn.Module):
     def __init__(self, alpha=0.25, gamma=2.0, fg_weight=13, bg_weight=1, downsample_factor=1):
         super().__init__()
@@ -86,16 +102,22 @@ class DDNLoss(nn.Module):
             start += n
         return canvas
 
-    def forward_padded(self, depth_logits, boxes_padded, depth_padded, valid):
+    def forward_padded(self, depth_logits, boxes_padded, depth_padded, valid, box_weight=None):
         """Same loss from padded per-image targets ([B,N,4] xyxy in depth-map pixels, [B,N], [B,N] bool) with no
         host round trip.  Equal depths aside (where the painted value is the same anyway) it reproduces
-        ``forward`` exactly; downsample_factor must be 1 (the only value the reference uses)."""
+        ``forward`` exactly; downsample_factor must be 1 (the only value the reference uses).
+        ``box_weight`` [B,N]: per-box weights -- a foreground pixel weighs fg_weight times the weight of the lowest slot among its
+        covering boxes of the nearest depth (``rasterize_box_weights``); the painted depth, the background and the divisor stay."""
         assert self.downsample_factor == 1
         B, _, H, W = depth_logits.shape
         if FUSED_DDN:
             from ..pointwise import ddn_loss, ddn_loss_supported
-            if ddn_loss_supported(depth_logits, boxes_padded, depth_padded, valid):
+            if ddn_loss_supported(depth_logits, boxes_padded, depth_padded, valid) and \
+                    (box_weight is None or box_weight.dtype == torch.float32):
                 # rasterisation, LID binning, softmax focal loss and balancing: one HIP kernel each way (csrc/ddn_loss.hip)
+                if box_weight is not None:
+                    return ddn_loss(depth_logits, boxes_padded, depth_padded, valid, self.alpha, self.gamma, self.fg_weight, self.bg_weight,
+                                    weight=box_weight)
                 return ddn_loss(depth_logits, boxes_padded, depth_padded, valid, self.alpha, self.gamma, self.fg_weight, self.bg_weight)
         b = boxes_padded.clone()
         b[..., :2] = torch.floor(b[..., :2])
@@ -103,10 +125,17 @@ class DDNLoss(nn.Module):
         depth_maps, fg = rasterize_boxes(b.long(), depth_padded, valid, H, W)
         target = lid_bin_indices(depth_maps, target=True)
         loss = softmax_focal_loss(depth_logits, target, self.alpha, self.gamma)
-        loss = loss * (self.fg_weight * fg + self.bg_weight * (~fg))
+        if box_weight is not None:
+            wmap = rasterize_box_weights(b.long(), depth_padded, valid, box_weight.to(loss.dtype), H, W)
+            loss = loss * (self.fg_weight * fg * wmap + self.bg_weight * (~fg))
+        else:
+            loss = loss * (self.fg_weight * fg + self.bg_weight * (~fg))
         return (loss * fg).sum() / fg.numel() + (loss * (~fg)).sum() / fg.numel()
 
-    def forward(self, depth_logits, gt_boxes2d, num_gt_per_img, gt_center_depth):
+    def forward(self, depth_logits, gt_boxes2d, num_gt_per_img, gt_center_depth, box_weight=None):
+        """``box_weight`` [sum(num_gt_per_img)]: per-box weights, see ``forward_padded``."""
+        if box_weight is not None:
+            return self._forward_weighted(depth_logits, gt_boxes2d, num_gt_per_img, gt_center_depth, box_weight)
         B, _, H, W = depth_logits.shape
         boxes_int = _int_boxes(gt_boxes2d)
         depth_maps = self.paint_boxes((B, H, W), boxes_int, num_gt_per_img, gt_center_depth,
@@ -121,6 +150,41 @@ class DDNLoss(nn.Module):
         num_pixels = fg.numel()
         loss = loss * weights
         return (loss * fg).sum() / num_pixels + (loss * (~fg)).sum() / num_pixels
+
+    def _forward_weighted(self, depth_logits, gt_boxes2d, num_gt_per_img, gt_center_depth, box_weight):
+        """``DDNLoss.forward`` with per-box weights: the painted depth and the foreground mask are ``forward``'s; the weight of a
+        foreground pixel follows the slot rule of ``rasterize_box_weights``."""
+        B, _, H, W = depth_logits.shape
+        boxes_int = _int_boxes(gt_boxes2d)
+        depth_maps = self.paint_boxes((B, H, W), boxes_int, num_gt_per_img, gt_center_depth, dtype=depth_logits.dtype, device=depth_logits.device)
+        target = lid_bin_indices(depth_maps, target=True)
+        loss = softmax_focal_loss(depth_logits, target, self.alpha, self.gamma)
+        boxes_fg = _int_boxes(boxes_int.to(gt_boxes2d.dtype) / self.downsample_factor)
+        fg = self.paint_boxes((B, H, W), boxes_fg, num_gt_per_img, None, dtype=torch.bool, device=loss.device)
+        pb, valid = _pad_per_image(boxes_fg, num_gt_per_img)
+        pd, _ = _pad_per_image(gt_center_depth.reshape(-1), num_gt_per_img)
+        pw, _ = _pad_per_image(box_weight.reshape(-1).to(loss.dtype), num_gt_per_img)
+        wmap = rasterize_box_weights(pb, pd, valid, pw, H, W)
+        weights = self.fg_weight * fg * wmap + self.bg_weight * (~fg)
+        num_pixels = fg.numel()
+        loss = loss * weights
+        return (loss * fg).sum() / num_pixels + (loss * (~fg)).sum() / num_pixels
+
+
+def rasterize_box_weights(boxes_int, depths, valid, weights, H, W):
+    """[B,H,W]: for every pixel the weight of the LOWEST slot among its valid covering boxes of the nearest depth (the scan of
+    csrc/ddn_loss.hip: slot order, strict <); 1 where no box covers.  Arguments as ``rasterize_boxes`` plus weights [B,N]."""
+    u1, v1, u2, v2 = boxes_int.unbind(-1)
+    ys = torch.arange(H, device=boxes_int.device).view(1, 1, H, 1)
+    xs = torch.arange(W, device=boxes_int.device).view(1, 1, 1, W)
+    y0, y1 = _norm_slice(v1, H)[..., None, None], _norm_slice(v2, H)[..., None, None]
+    x0, x1 = _norm_slice(u1, W)[..., None, None], _norm_slice(u2, W)[..., None, None]
+    cover = (ys >= y0) & (ys < y1) & (xs >= x0) & (xs < x1) & valid[..., None, None]          # [B,N,H,W]
+    inf = torch.full((), float("inf"), dtype=depths.dtype, device=depths.device)
+    d = torch.where(cover, depths[..., None, None], inf)
+    first = (cover & (d == d.amin(dim=1, keepdim=True))).to(torch.uint8).argmax(dim=1)         # first maximum = lowest slot
+    w = torch.gather(weights[..., None, None].expand(-1, -1, H, W), 1, first.unsqueeze(1)).squeeze(1)
+    return torch.where(cover.any(dim=1), w, torch.ones((), dtype=weights.dtype, device=weights.device))
 
 
 def _norm_slice(a, n):

@@ -16,7 +16,8 @@ SYMBOLS = ("mono_bias_act_f32", "mono_bias_relu_maxpool_nhwc_f32", "mono_conv1x1
            "mono_ddn_loss_fwd_f32", "mono_ddn_loss_bwd_f32", "mono_depth_expect_fwd_f32", "mono_depth_expect_bwd_f32", "mono_focal_fwd_f32", "mono_focal_bwd_f32", "mono_head_tail_fwd_f32", "mono_head_tail_bwd_f32", "mono_match_cost_f32", "mono_refine_reference_f32", "mono_relu_dropout_bwd_colsum_f32", "mono_sum_slices_f32", "mono_colsum_any_blocks", "mono_colsum_any_f32", "mono_relu_grad_mask3_f32", "mono_lsap_match_flat_f32",
            "mono_linear_wgrad_workspace", "mono_linear_wgrad_f32", "mono_colsum_levels_blocks", "mono_colsum_levels_f32", "mono_relu_grad_scale_f32",
            "mono_set_deterministic", "mono_groupnorm_stats_doubles", "mono_groupnorm_part_doubles", "mono_grad_accumulate_f32", "mono_ema_update_f32", "mono_step_stats_f32",
-           "mono_label_audit_f32")
+           "mono_label_audit_f32", "mono_matched_losses_weighted_fwd_f32", "mono_matched_losses_weighted_bwd_f32", "mono_focal_weighted_fwd_f32",
+           "mono_focal_weighted_bwd_f32", "mono_ddn_loss_weighted_fwd_f32", "mono_ddn_loss_weighted_bwd_f32", "mono_focal_weighted_max_cells")
 _lib = None
 
 
@@ -141,6 +142,20 @@ def load():
         lib.mono_refine_reference_f32.argtypes = [P, P, P, I, I, P]
         lib.mono_lsap_match_flat_f32.restype = I
         lib.mono_lsap_match_flat_f32.argtypes = [P, I, I, I, I, I, P, P, LL, P, P]
+        lib.mono_matched_losses_weighted_fwd_f32.restype = I
+        lib.mono_matched_losses_weighted_fwd_f32.argtypes = [P] * 13 + [I] * 4 + [P]
+        lib.mono_matched_losses_weighted_bwd_f32.restype = I
+        lib.mono_matched_losses_weighted_bwd_f32.argtypes = [P] * 17 + [I] * 4 + [P]
+        lib.mono_focal_weighted_max_cells.restype = I
+        lib.mono_focal_weighted_max_cells.argtypes = []
+        lib.mono_focal_weighted_fwd_f32.restype = I
+        lib.mono_focal_weighted_fwd_f32.argtypes = [P] * 6 + [I] * 5 + [F, F, P]
+        lib.mono_focal_weighted_bwd_f32.restype = I
+        lib.mono_focal_weighted_bwd_f32.argtypes = [P] * 6 + [I] * 5 + [F, F, P]
+        lib.mono_ddn_loss_weighted_fwd_f32.restype = I
+        lib.mono_ddn_loss_weighted_fwd_f32.argtypes = [P] * 6 + [I] * 5 + [LL] * 3 + [F] * 6 + [P]
+        lib.mono_ddn_loss_weighted_bwd_f32.restype = I
+        lib.mono_ddn_loss_weighted_bwd_f32.argtypes = [P] * 7 + [I] * 5 + [LL] * 3 + [F] * 6 + [P]
         _lib = lib
     return _lib
 
@@ -1103,14 +1118,58 @@ class _MatchedLosses(torch.autograd.Function):
         return (g_boxes, g_depth, g_dims, g_angle) + (None,) * 6
 
 
+class _MatchedLossesWeighted(torch.autograd.Function):
+    """``_MatchedLosses`` with the per-label weights ``t_weight`` [T] (``mono_matched_losses_weighted_*``): the pair of flat target t
+    enters every sum, ``comp`` and every gradient times ``t_weight[t]``."""
+    @staticmethod
+    def forward(ctx, boxes, depth, dims, angle, idx, t_box, t_depth, t_size, t_bin, t_res, t_weight):
+        NL, B, Q, _ = boxes.shape
+        K = idx.size(2)
+        out = torch.empty((NL, 6), dtype=torch.float32, device=boxes.device)
+        comp = torch.empty(NL, dtype=torch.float32, device=boxes.device)
+        tensors = (boxes, depth, dims, angle, idx, t_box, t_depth, t_size, t_bin, t_res, t_weight)
+        with on_device(boxes.device):
+            code = load().mono_matched_losses_weighted_fwd_f32(*[t.data_ptr() for t in tensors], out.data_ptr(), comp.data_ptr(), NL, B,
+                                                               Q, K, raw_stream())
+        if code:
+            raise RuntimeError("mono_matched_losses_weighted_fwd_f32 failed with code %d" % code)
+        ctx.save_for_backward(*tensors, comp)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        *tensors, comp = ctx.saved_tensors
+        boxes = tensors[0]
+        NL, B, Q, _ = boxes.shape
+        K = tensors[4].size(2)
+        buf = torch.zeros((NL, B, Q, 35), dtype=torch.float32, device=boxes.device)       # one memset for the four gradients
+        flat = buf.view(-1)
+        n = NL * B * Q
+        g_boxes, g_depth = flat[:n * 6].view(NL, B, Q, 6), flat[n * 6:n * 8].view(NL, B, Q, 2)
+        g_dims, g_angle = flat[n * 8:n * 11].view(NL, B, Q, 3), flat[n * 11:].view(NL, B, Q, 24)
+        go = go.contiguous()
+        with on_device(boxes.device):
+            code = load().mono_matched_losses_weighted_bwd_f32(*[t.data_ptr() for t in tensors], comp.data_ptr(), go.data_ptr(),
+                                                               g_boxes.data_ptr(), g_depth.data_ptr(), g_dims.data_ptr(),
+                                                               g_angle.data_ptr(), NL, B, Q, K, raw_stream())
+        if code:
+            raise RuntimeError("mono_matched_losses_weighted_bwd_f32 failed with code %d" % code)
+        return (g_boxes, g_depth, g_dims, g_angle) + (None,) * 7
+
+
 def matched_losses_supported(boxes, idx):
     return boxes.is_cuda and boxes.dtype == torch.float32 and idx.size(2) > 0
 
 
-def matched_losses(boxes, depth, dims, angle, idx, t_box, t_depth, t_size, t_bin, t_res):
-    """Per-layer sums [NL, 6] of {center, bbox, giou, depth, dim, angle} over the matched pairs ``idx`` [3, NL, K]."""
+def matched_losses(boxes, depth, dims, angle, idx, t_box, t_depth, t_size, t_bin, t_res, weight=None):
+    """Per-layer sums [NL, 6] of {center, bbox, giou, depth, dim, angle} over the matched pairs ``idx`` [3, NL, K].  ``weight`` [T]:
+    every pair of flat target t times ``weight[t]`` (the weighted kernels); None: the unweighted launches."""
     c = lambda t, dt: t.to(dt).contiguous()
     f = torch.float32
+    if weight is not None:
+        return _MatchedLossesWeighted.apply(c(boxes, f), c(depth, f), c(dims, f), c(angle, f), c(idx, torch.int64), c(t_box, f),
+                                            c(t_depth.reshape(-1), f), c(t_size, f), c(t_bin.reshape(-1), torch.int64),
+                                            c(t_res.reshape(-1), f), c(weight.reshape(-1), f))
     return _MatchedLosses.apply(c(boxes, f), c(depth, f), c(dims, f), c(angle, f), c(idx, torch.int64), c(t_box, f),
                                 c(t_depth.reshape(-1), f), c(t_size, f), c(t_bin.reshape(-1), torch.int64), c(t_res.reshape(-1), f))
 
@@ -1181,7 +1240,60 @@ class _DDNLoss(torch.autograd.Function):
         return (grad,) + (None,) * 9
 
 
-def ddn_loss(logits, boxes, depth, valid, alpha, gamma, fg_weight, bg_weight, depth_min=1e-3, depth_max=60.0):
+class _DDNLossWeighted(torch.autograd.Function):
+    """``_DDNLoss`` with per-box weights ``box_weight`` [B, N] (``mono_ddn_loss_weighted_*``), eager backward included."""
+    @staticmethod
+    def forward(ctx, logits, boxes, depth, valid, box_weight, alpha, gamma, fg_weight, bg_weight, depth_min, depth_max):
+        B, C, H, W = logits.shape
+        N = boxes.shape[1]
+        boxes, depth, valid, box_weight = boxes.contiguous(), depth.contiguous(), valid.contiguous(), box_weight.contiguous()
+        sb, sc, sp = _ddn_strides(logits)
+        lib = load()
+        partial = torch.empty(lib.mono_ddn_loss_blocks(B, H, W), dtype=torch.float32, device=logits.device)
+        code = lib.mono_ddn_loss_weighted_fwd_f32(logits.data_ptr(), boxes.data_ptr(), depth.data_ptr(), valid.data_ptr(),
+                                                  box_weight.data_ptr(), partial.data_ptr(), B, C, H, W, N, sb, sc, sp, alpha, gamma,
+                                                  fg_weight, bg_weight, depth_min, depth_max, raw_stream())
+        if code:
+            raise RuntimeError("mono_ddn_loss_weighted_fwd_f32 failed with code %d" % code)
+        ctx.consts = (alpha, gamma, fg_weight, bg_weight, depth_min, depth_max)
+        ctx.eager = None
+        if DDN_EAGER_BACKWARD and logits.requires_grad:          # as in _DDNLoss.forward: evaluated under the matcher's wait
+            one = torch.ones(1, dtype=torch.float32, device=logits.device)
+            grad = torch.empty_strided(logits.shape, logits.stride(), dtype=logits.dtype, device=logits.device)
+            code = lib.mono_ddn_loss_weighted_bwd_f32(logits.data_ptr(), boxes.data_ptr(), depth.data_ptr(), valid.data_ptr(),
+                                                      box_weight.data_ptr(), one.data_ptr(), grad.data_ptr(), B, C, H, W, N, sb, sc, sp,
+                                                      *ctx.consts, raw_stream())
+            if code:
+                raise RuntimeError("mono_ddn_loss_weighted_bwd_f32 failed with code %d" % code)
+            ctx.save_for_backward(grad)
+            ctx.eager = True
+        else:
+            ctx.save_for_backward(logits, boxes, depth, valid, box_weight)
+        return partial.sum() / (B * H * W)
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.eager:
+            (grad,) = ctx.saved_tensors
+            return (grad * g,) + (None,) * 10
+        logits, boxes, depth, valid, box_weight = ctx.saved_tensors
+        B, C, H, W = logits.shape
+        sb, sc, sp = _ddn_strides(logits)
+        grad = torch.empty_strided(logits.shape, logits.stride(), dtype=logits.dtype, device=logits.device)
+        g = g.reshape(1).to(torch.float32).contiguous()
+        code = load().mono_ddn_loss_weighted_bwd_f32(logits.data_ptr(), boxes.data_ptr(), depth.data_ptr(), valid.data_ptr(),
+                                                     box_weight.data_ptr(), g.data_ptr(), grad.data_ptr(), B, C, H, W, boxes.shape[1],
+                                                     sb, sc, sp, *ctx.consts, raw_stream())
+        if code:
+            raise RuntimeError("mono_ddn_loss_weighted_bwd_f32 failed with code %d" % code)
+        return (grad,) + (None,) * 10
+
+
+def ddn_loss(logits, boxes, depth, valid, alpha, gamma, fg_weight, bg_weight, depth_min=1e-3, depth_max=60.0, weight=None):
+    """``weight`` [B, N] float32: per-box weights (the weighted kernels); None: the unweighted launches."""
+    if weight is not None:
+        return _DDNLossWeighted.apply(logits, boxes, depth, valid, weight.to(torch.float32), float(alpha), float(gamma),
+                                      float(fg_weight), float(bg_weight), float(depth_min), float(depth_max))
     return _DDNLoss.apply(logits, boxes, depth, valid, float(alpha), float(gamma), float(fg_weight), float(bg_weight),
                           float(depth_min), float(depth_max))
 
@@ -1253,14 +1365,59 @@ class _FocalClassification(torch.autograd.Function):
         return grad, None, None, None, None, None
 
 
+class _FocalClassificationWeighted(torch.autograd.Function):
+    """``_FocalClassification`` with the per-label weights ``t_weight`` [T] (``mono_focal_weighted_*``): the C terms of a matched cell
+    times the weight of its target; the two logging columns stay unweighted."""
+    @staticmethod
+    def forward(ctx, logits, idx, labels, sizes, t_weight, alpha, gamma):
+        NL, B, Q, C = logits.shape
+        K = idx.size(2)
+        out = torch.empty((NL, 3), dtype=torch.float32, device=logits.device)
+        with on_device(logits.device):
+            code = load().mono_focal_weighted_fwd_f32(logits.data_ptr(), idx.data_ptr(), labels.data_ptr(), sizes.data_ptr(),
+                                                      t_weight.data_ptr(), out.data_ptr(), NL, B, Q, C, K, alpha, gamma, raw_stream())
+        if code:
+            raise RuntimeError("mono_focal_weighted_fwd_f32 failed with code %d" % code)
+        ctx.save_for_backward(logits, idx, labels, t_weight)
+        ctx.consts = (alpha, gamma)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        logits, idx, labels, t_weight = ctx.saved_tensors
+        NL, B, Q, C = logits.shape
+        g = go[:, 0].contiguous()                       # class / cardinality errors carry no gradient
+        grad = torch.empty_like(logits)
+        with on_device(logits.device):
+            code = load().mono_focal_weighted_bwd_f32(logits.data_ptr(), idx.data_ptr(), labels.data_ptr(), t_weight.data_ptr(),
+                                                      g.data_ptr(), grad.data_ptr(), NL, B, Q, C, idx.size(2), *ctx.consts, raw_stream())
+        if code:
+            raise RuntimeError("mono_focal_weighted_bwd_f32 failed with code %d" % code)
+        return grad, None, None, None, None, None, None
+
+
 def focal_classification_supported(logits, idx):
     NL, B, Q, C = logits.shape
     return logits.is_cuda and logits.dtype == torch.float32 and C <= 255 and B <= 256 and B * Q <= 32768 and idx.size(2) > 0
 
 
-def focal_classification(logits, idx, labels, sizes, alpha, gamma=2.0):
+FOCAL_WEIGHTED_MAX_CELLS = 16384      # B * Q of the weighted focal kernels (mono_focal_weighted_max_cells: class + pair per cell in LDS)
+
+
+def focal_classification_weighted_supported(logits, idx):
+    NL, B, Q, C = logits.shape
+    return logits.is_cuda and logits.dtype == torch.float32 and C <= 255 and B <= 256 and B * Q <= FOCAL_WEIGHTED_MAX_CELLS \
+        and 0 < idx.size(2) < 65535
+
+
+def focal_classification(logits, idx, labels, sizes, alpha, gamma=2.0, weight=None):
     """-> [NL, 3]: per decoder layer the sigmoid-focal-loss SUM against the matched one-hot targets (differentiable), the
-    class error in % and the cardinality error (monodetr.py:396-449) -- one HIP launch each way."""
+    class error in % and the cardinality error (monodetr.py:396-449) -- one HIP launch each way.  ``weight`` [T]: the terms of a
+    matched cell times the weight of its target (the weighted kernels); None: the unweighted launches."""
+    if weight is not None:
+        return _FocalClassificationWeighted.apply(logits.contiguous(), idx.contiguous(), labels.to(torch.int64).contiguous(),
+                                                  sizes.to(torch.float32).contiguous(), weight.reshape(-1).to(torch.float32).contiguous(),
+                                                  float(alpha), float(gamma))
     return _FocalClassification.apply(logits.contiguous(), idx.contiguous(), labels.to(torch.int64).contiguous(),
                                       sizes.to(torch.float32).contiguous(), float(alpha), float(gamma))
 

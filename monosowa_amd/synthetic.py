@@ -115,11 +115,33 @@ def attach_host_mask(mask_device, mask_host):
     return mask_device
 
 
+def attach_host_weight(weight_device, weight_host):
+    """The per-label weights on the host next to their device copy, like ``attach_host_mask``: ``prepare_targets`` and the Trainer form
+    the weighted normaliser from them without a device->host sync."""
+    weight_device._host_weight = np.asarray(weight_host, dtype=np.float32)
+    return weight_device
+
+
+def host_label_weight(targets):
+    """The host copy of ``targets["label_weight"]`` ([B, max_objs] float32): the tensor itself when it lives on the host, else what
+    ``attach_host_weight`` left beside it; a device-resident batch without one is refused (nothing here may wait for the device)."""
+    w = targets["label_weight"]
+    host = getattr(w, "_host_weight", None)
+    if host is None:
+        if w.is_cuda:
+            raise ValueError("the weighted normaliser adds the label weights up on the host: a device-resident batch needs "
+                             "synthetic.attach_host_weight on its label_weight")
+        host = w.detach().numpy()
+    return host
+
+
 def prepare_targets(targets, batch_size):
     """Padded [B,50,...] dict -> list of per-image dicts of the valid objects (trainer_helper.py:180-191).
     The reference indexes every key of every image with a boolean mask (8 x B device->host syncs); here the
-    mask is resolved once and each key is gathered once for the whole batch, then split into views."""
-    keys = ("labels", "boxes", "calibs", "depth", "size_3d", "heading_bin", "heading_res", "boxes_3d")
+    mask is resolved once and each key is gathered once for the whole batch, then split into views.
+    With ``label_weight`` in the dict (dataset.label_weights) it is gathered like the other keys and ``weight_sum`` holds the sum of
+    the valid labels' weights, formed on the host."""
+    keys = ("labels", "boxes", "calibs", "depth", "size_3d", "heading_bin", "heading_res", "boxes_3d", "label_weight")
     host = getattr(targets["mask_2d"], "_host_mask", None)
     if host is not None and USE_HOST_MASK:
         hb, hs = np.nonzero(host[:batch_size])                     # row-major = per image, slot order; no device sync
@@ -135,9 +157,18 @@ def prepare_targets(targets, batch_size):
     per_key = {k: v.split(counts) for k, v in flat.items()}
     out = TargetList({k: per_key[k][b] for k in per_key} for b in range(batch_size))
     out.flat = flat                 # the per-image entries are views of these: the criterion need not concatenate them again
+    if "label_weight" in targets:
+        from .monodetr.criterion import label_weight_sum
+        if host is None or not USE_HOST_MASK:
+            host = targets["mask_2d"].cpu().numpy() if not targets["mask_2d"].is_cuda else None
+        if host is None:
+            raise ValueError("the weighted normaliser adds the label weights up on the host: a device-resident batch needs "
+                             "synthetic.attach_host_mask on its mask_2d")
+        out.weight_sum = label_weight_sum(host_label_weight(targets)[:batch_size], np.asarray(host, dtype=bool)[:batch_size])
     return out
 
 
 class TargetList(list):
     """The reference's list of per-image target dicts, remembering the batch-flat tensors its entries are views of."""
     flat = None
+    weight_sum = None      # host float: sum of the valid labels' weights when the batch carries label_weight

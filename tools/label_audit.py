@@ -2,6 +2,7 @@
 
     python tools/label_audit.py report DIR [--last E] [--by COLUMN] [--top N] [--csv FILE]
     python tools/label_audit.py scan --config CFG --checkpoint FILE [--weights ema] [--split SPLIT] [--out FILE] [--workers N]
+    python tools/label_audit.py weights DIR --out FILE [--last E] [--by COLUMN] (--huber X | --drop-above X)
 
 ``report`` merges the ``epoch_NNN.npz`` / ``epoch_NNN.rankR.npz`` files of ``DIR`` (``<output_dir>/label_audit``): every column is
 averaged per ``(img_id, line)`` over the rows of the last ``E`` epochs found (all of them by default; ``count`` is the mean number of
@@ -10,6 +11,10 @@ front), written to a CSV (default ``DIR/report.csv``) and the top ``N`` printed.
 
 ``scan`` audits a label set with a trained checkpoint: one pass of ``LabelAudit.scan`` in eval mode over ``--split`` (default: the
 config's ``train_split``), every label paired with one query, into one ``.npz`` that ``report`` reads too.
+
+``weights`` turns ``report``'s per-label means of ``--by`` into the CSV that ``dataset.label_weights`` reads (``img_id,line,weight``):
+``--huber X`` gives 1 where the value is <= X and X / value beyond it (the IRLS weight that bounds an L1 term at X), ``--drop-above X``
+gives 0 where the value is > X and 1 elsewhere; a NaN value gives 0; X must be positive.
 
 The terms are measured in the frame of the step's augmentation (flip, crop, canonical depth), and only labels that pass the dataset's
 filter and ``mask_2d`` ever appear."""
@@ -99,6 +104,36 @@ def _report(args):
         print("%12s %5d %4d %5d  " % (r["img_id"], r["line"], r["cls"], r["seen"]) + " ".join("%10.4g" % r[c] for c in columns))
 
 
+def label_weights(values, huber=None, drop_above=None):
+    """The weight of every per-label value: ``huber`` X -> 1 where value <= X else X / value; ``drop_above`` X -> 0 where value > X
+    else 1; NaN -> 0.  Exactly one of the two, X > 0."""
+    if (huber is None) == (drop_above is None):
+        raise ValueError("give exactly one of --huber and --drop-above")
+    x = float(huber if huber is not None else drop_above)
+    if not x > 0 or not np.isfinite(x):
+        raise ValueError("the threshold of --huber / --drop-above must be positive and finite, got %r" % (x,))
+    v = np.asarray(values, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = np.where(v <= x, 1.0, x / v) if huber is not None else np.where(v > x, 0.0, 1.0)
+    return np.where(np.isnan(v), 0.0, w)
+
+
+def write_weights(path, rows, weights):
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["img_id", "line", "weight"])
+        for r, x in zip(rows, weights):
+            w.writerow([r["img_id"], r["line"], repr(float(x))])
+
+
+def _weights(args):
+    _, rows = report(args.dir, args.last, args.by)
+    w = label_weights([r[args.by] for r in rows], args.huber, args.drop_above)
+    write_weights(args.out, rows, w)
+    print("%d labels by %s -> %s: %d at weight 1, %d at weight 0, %d between" % (
+        len(rows), args.by, args.out, int((w == 1).sum()), int((w == 0).sum()), int(((w > 0) & (w < 1)).sum())))
+
+
 def _scan(args):
     from monosowa_amd import miopen_tuning
     miopen_tuning.use_shipped_db(0)
@@ -152,7 +187,20 @@ def main(argv=None):
     s.add_argument("--out", default=None)
     s.add_argument("--workers", type=int, default=4)
     s.set_defaults(run=_scan)
+    w = sub.add_parser("weights", help="per-label loss weights (dataset.label_weights) from a label_audit directory")
+    w.add_argument("dir")
+    w.add_argument("--out", required=True)
+    w.add_argument("--last", type=int, default=None, help="epochs to average over, counted from the last one found (default: all)")
+    w.add_argument("--by", default="depth_abs")
+    how = w.add_mutually_exclusive_group(required=True)
+    how.add_argument("--huber", type=float, default=None, metavar="X", help="weight 1 up to X, X / value beyond")
+    how.add_argument("--drop-above", type=float, default=None, metavar="X", help="weight 0 beyond X, 1 up to it")
+    w.set_defaults(run=_weights)
     args = ap.parse_args(argv)
+    if args.command == "weights":
+        x = args.huber if args.huber is not None else args.drop_above
+        if not x > 0:
+            ap.error("the threshold of --huber / --drop-above must be positive, got %r" % (x,))
     args.run(args)
 
 
