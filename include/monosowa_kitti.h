@@ -37,6 +37,23 @@ int mono_extract_dets_f32(const float *logits, const float *boxes, const float *
 int mono_decode_dets_f64(const float *dets, const double *geom, const double *cls_mean_size, double threshold, double *rows,
                          int *count, int B, int K, int C, void *stream);
 
+/* Duplicate suppression by rotated BEV overlap and fusion of the mirrored view (tester.nms_iou / flip_tta / fuse), one kernel on
+ * mono_decode_dets_f64's rows.  rows f64 [V*B, K, 14] and count [V*B]: view v of image b at index v*B + b, view 1 decoded from the
+ * mirrored frame with the image's own geometry row; geom f64 [B, 10].  Candidates: id j for view 0, K + j for view 1 brought back
+ * into the frame (x1' = W - x2, x2' = W - x1, alpha' = wrap(pi - alpha), x' = ((W - 2 cu) z) / fu - x + 2 tx,
+ * ry' = wrap(alpha' + atan2((x1' + x2') / 2 - cu, fu)); double, unfused).  Order: score descending, exact ties by lower id, NaN
+ * last.  A candidate joins the first seed of its class whose BEV rectangle (x, z, l, w, ry; float32, the evaluation's
+ * intersection routine, criterion -1; two rectangles equal in all five float32 numbers, finite, overlap by 1; a
+ * rectangle with a side that is not > 0 overlaps nothing) it overlaps by IoU >= iou (float32 compare; NaN never matches), else it
+ * becomes a seed.
+ * out_rows f64 [B, V*K, 14]: one row per seed in seed order, zeros behind; out_count int32 [B]; out_support int32 [B, V*K]: members
+ * per cluster.  mode 0: the seed's row, byte for byte.  mode 1: columns x1..z = sum(w v) / sum(w) over the members in order with
+ * w = score, ry = atan2(sum w sin ry, sum w cos ry), alpha = wrap(ry - atan2((x1 + x2) / 2 - cu, fu)), cls the seed's,
+ * score = (best member score of view 0 + of view 1, 0 without a member) / V.  V in {1, 2}, V*K <= 256, iou in (0, 1];
+ * otherwise -2. */
+int mono_fuse_dets_f64(const double *rows, const int *count, const double *geom, double iou, int mode, double *out_rows,
+                       int *out_count, int *out_support, int B, int K, int V, void *stream);
+
 /* KITTI AP accumulation, HOST functions: the official matching protocol as kitti_eval_python/eval.py:234-410
  * runs it (numba there), one call per (class, difficulty, min_overlap) over all images.  Host pointers.
  *   n_gt / n_dt / n_dc [n_images]: boxes per image;   overlaps: the images' [n_dt, n_gt] matrices (row = detection), concatenated;

@@ -6,6 +6,9 @@
     for ids, rows in det.stream(batches): ...       # batches: an iterable of (frames, P2)
     det.write_kitti(rows, ids, directory)           # the files Tester.save_results writes
 
+With ``tester.nms_iou`` (and ``tester.flip_tta`` / ``tester.fuse``) in the configuration the rows are suppressed / fused on the device
+first (monosowa_amd/fuse.py); ``det.detect(frames, P2, support=True)`` also returns how many candidates each row stands for.
+
 ``rows[i]`` is float64 ``[n_i, 14]`` in ``decode_detections``' column order: cls, alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry,
 score.  Frames run on monosowa_amd/inference.py's ``InferenceEngine`` like ``Tester.inference``'s batches (image preparation,
 graph-replayed forward and detection extraction on the GPU); the rows are decoded on the device as well
@@ -20,6 +23,7 @@ import os
 import numpy as np
 import torch
 
+from .fuse import fuse_config
 from .helpers.save_helper import load_checkpoint, unwrap
 from .image_prep import collate_raw, make_record
 from .inference import InferenceEngine
@@ -83,8 +87,10 @@ class Detector:
         self.class_name = self.dataset.class_name
         self.threshold = cfg["tester"].get("threshold", 0.2)
         self.topk = cfg["tester"]["topk"]
+        # tester.nms_iou / flip_tta / fuse: duplicate suppression and flip-view fusion of the rows (monosowa_amd/fuse.py); None: off
+        self.fuse = fuse_config(cfg["tester"])
         self.engine = InferenceEngine(self.model, self.device, topk=self.topk, max_objs=self.dataset.max_objs,
-                                      decode=(self.dataset.cls_mean_size, self.threshold))
+                                      decode=(self.dataset.cls_mean_size, self.threshold), fuse=self.fuse)
 
     def _batch(self, frames, P2, first_id):
         """(frames, P2) -> what ``engine.submit`` takes: the raw canvas and default-collated info, as a ``device_aug`` loader's
@@ -112,6 +118,12 @@ class Detector:
         """``batches``: an iterable of ``(frames, P2)``, one engine batch each.  Yields ``(ids, rows)`` per batch in order, as the
         batches complete: ``ids`` are the frames' running indices, ``rows[i]`` float64 ``[n_i, 14]``.  The weights the model holds
         when the call starts are the ones used."""
+        for done in self._completed(batches):
+            yield done.tag, [done.rows[i, :done.count[i]] for i in range(len(done.tag))]
+
+    @torch.no_grad()
+    def _completed(self, batches):
+        """``stream``'s loop: the engine's ``Completed`` batches in order, ``tag`` = the frames' running indices."""
         self.engine.sync_weights()
         n = 0
         try:
@@ -122,16 +134,15 @@ class Detector:
                 canvas, calibs, info, geom = self._batch(frames, P2, n)
                 ids = list(range(n, n + len(frames)))
                 n += len(frames)
-                for done in self.engine.submit(canvas, calibs, info["img_size"], info["height_crop"], prep=info["prep"], geom=geom,
-                                               tag=ids):
-                    yield done.tag, [done.rows[i, :done.count[i]] for i in range(len(done.tag))]
-            for done in self.engine.drain():
-                yield done.tag, [done.rows[i, :done.count[i]] for i in range(len(done.tag))]
+                yield from self.engine.submit(canvas, calibs, info["img_size"], info["height_crop"], prep=info["prep"], geom=geom, tag=ids)
+            yield from self.engine.drain()
         finally:
             self.engine.abandon()                       # left early (an exception, or the consumer stopped): nothing stays in flight
 
-    def detect(self, frames, P2, batch_size=16):
-        """All frames, ``batch_size`` at a time -> ``rows``: one float64 ``[n_i, 14]`` array per frame."""
+    def detect(self, frames, P2, batch_size=16, support=False):
+        """All frames, ``batch_size`` at a time -> ``rows``: one float64 ``[n_i, 14]`` array per frame.  With the fuse keys set the
+        rows are the fused ones; ``support=True`` -> ``(rows, support)``, ``support[i]`` int32 ``[n_i]``: how many candidates each
+        row stands for (1 everywhere with the keys off)."""
         frames = list(frames)
         P2 = np.asarray(P2)
         if P2.ndim == 2:
@@ -139,10 +150,12 @@ class Detector:
         if P2.shape != (len(frames), 3, 4):
             raise ValueError("P2 must be [%d, 3, 4] (one matrix per frame) or [3, 4], got %s" % (len(frames), P2.shape))
         chunks = ((frames[i:i + batch_size], P2[i:i + batch_size]) for i in range(0, len(frames), int(batch_size)))
-        out = []
-        for _, rows in self.stream(chunks):
-            out.extend(rows)
-        return out
+        out, members = [], []
+        for done in self._completed(chunks):
+            for i in range(len(done.tag)):
+                out.append(done.rows[i, :done.count[i]])
+                members.append(np.ones(done.count[i], dtype=np.int32) if done.support is None else done.support[i, :done.count[i]])
+        return (out, members) if support else out
 
     def write_kitti(self, rows, ids, directory):
         """One KITTI result file per frame, ``%06d.txt`` of its id: the files ``Tester.save_results`` writes for these rows."""

@@ -62,6 +62,9 @@ class Tester(object):
         self.weights = cfg.get("weights", "model")
         if self.weights not in ("model", "ema"):
             raise ValueError("tester.weights must be 'model' or 'ema', got %r" % (self.weights,))
+        # tester.nms_iou / flip_tta / fuse: duplicate suppression and flip-view fusion on the device (monosowa_amd/fuse.py); None: off
+        from ..fuse import fuse_config
+        self.fuse = fuse_config(cfg)
 
     def test(self):
         assert self.cfg["mode"] in ["single", "all"]
@@ -103,12 +106,36 @@ class Tester(object):
                 results.update(decode_detections(dets=done.dets, info=info_np, calibs=cal, cls_mean_size=dataset.cls_mean_size,
                                                  threshold=threshold))
 
-        engine = InferenceEngine(self.model, self.device, topk=self.cfg["topk"], max_objs=self.max_objs)
+        def cameras(calibs, info):
+            if hasattr(dataset, "get_calib"):
+                return [dataset.get_calib(int(i)) for i in info["img_id"]]
+            return [PinholeCalib(p) for p in calibs.numpy()]
+
+        def geometry(calibs, info):
+            """The rows ``mono_decode_dets_f64`` reads (include/monosowa_kitti.h), from what ``decode_detections`` reads."""
+            num = lambda v: v.numpy() if torch.is_tensor(v) else np.asarray(v)
+            return torch.from_numpy(np.array([[s[0], s[1], hc, cs, c.cu, c.cv, c.fu, c.fv, c.tx, c.ty] for s, hc, cs, c in
+                                              zip(num(info["img_size"]), num(info["height_crop"]), num(info["canonical_scale"]),
+                                                  cameras(calibs, info))], dtype=np.float64))
+
+        def consume_rows(batches):
+            """The fused rows of the engine, in ``decode_detections``' row type."""
+            for done in batches:
+                for i, img_id in enumerate(done.tag[1]["img_id"]):
+                    results[int(img_id)] = [[int(r[0])] + [float(v) for v in r[1:]] for r in done.rows[i, :done.count[i]]]
+
+        if self.fuse is not None:
+            consume = consume_rows
+            engine = InferenceEngine(self.model, self.device, topk=self.cfg["topk"], max_objs=self.max_objs,
+                                     decode=(dataset.cls_mean_size, threshold), fuse=self.fuse)
+        else:
+            engine = InferenceEngine(self.model, self.device, topk=self.cfg["topk"], max_objs=self.max_objs)
         bar = tqdm.tqdm(total=len(self.dataloader), leave=True, desc="Evaluation Progress")
         try:
             for inputs, calibs, targets, info in self.dataloader:
                 consume(engine.submit(inputs, calibs, info["img_size"], info["height_crop"],
-                                      prep=info["prep"] if is_raw_batch(inputs) else None, tag=(calibs, info)))
+                                      prep=info["prep"] if is_raw_batch(inputs) else None, tag=(calibs, info),
+                                      geom=None if self.fuse is None else geometry(calibs, info)))
                 bar.update()
             consume(engine.drain())
         finally:

@@ -9,7 +9,8 @@
 
 On a CUDA device a batch is: ``image_prep.prepare`` straight into the static input of a captured graph (or a copy of prepared
 images), one graph replay of the eval forward, ``mono_extract_dets_f32`` (and, when the caller gives per-image geometry,
-``mono_decode_dets_f64``) on the same stream, a non-blocking copy into a pinned host slot, an event.  ``submit`` returns after
+``mono_decode_dets_f64``, and with ``fuse=`` the duplicate suppression / flip-view fusion ``mono_fuse_dets_f64``) on the same stream,
+a non-blocking copy into a pinned host slot, an event.  ``submit`` returns after
 enqueueing; nothing synchronises the device: the consumer waits on the oldest slot's event only, and only when ``in_flight``
 batches are already queued.  One graph per batch size seen, at most ``MAX_GRAPHS``; further batch sizes run eagerly.  A capture
 that fails raises.  On a CPU device the same sequence runs eagerly inside ``submit``.  The device decides; there is no switch.
@@ -23,18 +24,21 @@ import numpy as np
 import torch
 
 from .helpers.decode_helper import decode_detections, extract_dets_from_outputs
-from .image_prep import RESOLUTION, is_raw_batch, prepare
+from .fuse import MAX_CANDIDATES, fuse_rows_device, fuse_rows_host
+from .image_prep import FLIP, RESOLUTION, is_raw_batch, prepare
 
 MAX_GRAPHS = 3
 
 
 class Completed:
     """One finished batch: ``tag`` as given to ``submit``; ``dets`` float32 ``[B, K, 37]``, or, for a batch submitted with
-    geometry, ``rows`` float64 ``[B, K, 14]`` (kept rows first) and ``count`` int32 ``[B]``.  Host arrays owned by the caller."""
-    __slots__ = ("tag", "dets", "rows", "count")
+    geometry, ``rows`` float64 ``[B, K, 14]`` (kept rows first) and ``count`` int32 ``[B]``; on an engine with ``fuse=`` the rows
+    are the fused ones, ``[B, V * K, 14]``, and ``support`` int32 ``[B, V * K]`` holds the members of each row's cluster.  Host arrays
+    owned by the caller."""
+    __slots__ = ("tag", "dets", "rows", "count", "support")
 
-    def __init__(self, tag, dets=None, rows=None, count=None):
-        self.tag, self.dets, self.rows, self.count = tag, dets, rows, count
+    def __init__(self, tag, dets=None, rows=None, count=None, support=None):
+        self.tag, self.dets, self.rows, self.count, self.support = tag, dets, rows, count, support
 
 
 class _Graph:
@@ -82,8 +86,11 @@ def weights_stamp(model):
 
 
 class InferenceEngine:
-    def __init__(self, model, device, topk=50, max_objs=50, in_flight=2, decode=None):
-        """``decode``: ``(cls_mean_size [C, 3], threshold)`` for batches submitted with ``geom`` (rows instead of detections)."""
+    def __init__(self, model, device, topk=50, max_objs=50, in_flight=2, decode=None, fuse=None):
+        """``decode``: ``(cls_mean_size [C, 3], threshold)`` for batches submitted with ``geom`` (rows instead of detections).
+        ``fuse``: ``(iou, flip_tta, mode)`` as ``fuse.fuse_config`` returns it -- every batch then comes with ``geom`` and its rows
+        are fused (monosowa_amd/fuse.py); with ``flip_tta`` the mirrored frames run in the same forward, as a second half of the
+        batch prepared from the same canvas with the records' FLIP bit toggled."""
         self.model = model.eval()
         self.device = torch.device(device)
         self.cuda = self.device.type == "cuda"
@@ -93,6 +100,11 @@ class InferenceEngine:
         if decode is not None:
             cms = torch.from_numpy(np.ascontiguousarray(decode[0], dtype=np.float64))
             self.decode = (cms.to(self.device), float(decode[1]))
+        self.fuse = None
+        if fuse is not None:
+            if self.decode is None:
+                raise ValueError("InferenceEngine(fuse=...) needs decode=(cls_mean_size, threshold): rows are what is fused")
+            self.fuse = (float(fuse[0]), bool(fuse[1]), fuse[2])
         self.graphs = collections.OrderedDict()              # (images shape, dtypes) -> _Graph
         self.stamp = None
         self.queue = collections.deque()                     # CUDA: (slot, tag, B, kind) in submission order; CPU: Completed
@@ -183,11 +195,57 @@ class InferenceEngine:
             slot.done.synchronize()
             self.model_seconds += slot.start.elapsed_time(slot.end) * 1e-3
             self.images += B
+            if geom == "fused":
+                return Completed(tag, rows=slot.buffers["rows"][:B].numpy().copy(), count=slot.buffers["count"][:B].numpy().copy(),
+                                 support=slot.buffers["support"][:B].numpy().copy())
+            if geom == "fuse on the host":                                # more candidates than the kernel takes
+                views = 2 if self.fuse[1] else 1
+                rows, count, support = fuse_rows_host(slot.buffers["rows"][:views * B].numpy(), slot.buffers["count"][:views * B].numpy(),
+                                                      slot.buffers["geom"][:B].numpy(), self.fuse[0], self.fuse[2], views)
+                return Completed(tag, rows=rows, count=count, support=support)
             if geom:
                 return Completed(tag, rows=slot.buffers["rows"][:B].numpy().copy(), count=slot.buffers["count"][:B].numpy().copy())
             return Completed(tag, dets=slot.buffers["dets"][:B].numpy().copy())
         finally:
             self.free_slots.append(slot)
+
+    def _forward_with_flip(self, inputs, prep, calibs, img_sizes, slot):
+        """``_forward`` of 2 B images: the frames, then the same frames mirrored -- the canvas goes to the device once and is
+        prepared twice, the second time with every record's FLIP bit toggled (flags + 1 - 2 (flags mod 2), on the device)."""
+        B = inputs.shape[0]
+        shape = (2 * B, 3, RESOLUTION[1], RESOLUTION[0])
+        key = (shape, calibs.dtype, img_sizes.dtype, "flip")
+        g = self.graphs.get(key)
+        eager = g is None and len(self.graphs) >= MAX_GRAPHS
+        images = g.images if g is not None else \
+            torch.empty(shape, dtype=torch.float32, device=self.device).contiguous(memory_format=torch.channels_last)
+        canvas = inputs.to(self.device, non_blocking=True)
+        records = prep.to(self.device, non_blocking=True)
+        mirrored = records.clone()
+        mirrored[:, 8] = records[:, 8] + 1 - 2 * torch.remainder(records[:, 8], 2)
+        assert FLIP == 1
+        prepare(canvas, records, self.device, out=images[:B])
+        prepare(canvas, mirrored, self.device, out=images[B:])
+        calibs, img_sizes = torch.cat([calibs, calibs]), torch.cat([img_sizes, img_sizes])
+        if eager:
+            slot.start.record()
+            with torch.no_grad():
+                outputs = self.model(images, calibs, None, img_sizes, dn_args=0)
+            slot.end.record()
+            self.eager_forwards += 1
+            return outputs
+        if g is None:
+            if not self.graphs:
+                self.stamp = weights_stamp(self.model)
+            g = self.graphs[key] = _Graph(self.model, images, calibs, img_sizes)
+        else:
+            g.calibs.copy_(calibs, non_blocking=True)
+            g.img_sizes.copy_(img_sizes, non_blocking=True)
+        slot.start.record()
+        g.graph.replay()
+        slot.end.record()
+        self.replays += 1
+        return g.outputs
 
     def _forward(self, inputs, prep, calibs, img_sizes, slot):
         """The eval forward on the current stream: graph replay for a cached (or cacheable) batch shape, eager otherwise."""
@@ -229,41 +287,74 @@ class InferenceEngine:
     def _enqueue(self, inputs, calibs, img_size, height_crop, prep, geom, tag):
         if geom is not None and self.decode is None:
             raise ValueError("a batch with geometry needs InferenceEngine(decode=(cls_mean_size, threshold))")
+        self._check_fuse(inputs, geom)
+        flip = self.fuse is not None and self.fuse[1]
+        kind = geom is not None
         slot = self.free_slots.pop()
         try:
             calibs_dev = calibs.to(self.device, non_blocking=True)
             img_sizes = self._img_sizes(img_size, height_crop)
-            outputs = self._forward(inputs, prep, calibs_dev, img_sizes, slot)
+            outputs = (self._forward_with_flip if flip else self._forward)(inputs, prep, calibs_dev, img_sizes, slot)
             dets = extract_dets_from_outputs(outputs=outputs, K=self.max_objs, topk=self.topk)
             if geom is not None:
                 from .kitti_eval import decode_dets_device
-                rows, count = decode_dets_device(dets.contiguous(), geom.to(self.device, non_blocking=True), *self.decode)
+                geom_dev = geom.to(self.device, non_blocking=True)
+                rows, count = decode_dets_device(dets.contiguous(), torch.cat([geom_dev, geom_dev]) if flip else geom_dev, *self.decode)
+                support = None
+                if self.fuse is not None:
+                    views = 2 if flip else 1
+                    if views * rows.shape[1] <= MAX_CANDIDATES:
+                        rows, count, support = fuse_rows_device(rows, count, geom_dev, self.fuse[0], self.fuse[2], views)
+                        kind = "fused"
+                    else:                                                 # fused in _complete, from the unfused rows
+                        slot.pinned("geom", geom_dev).copy_(geom_dev, non_blocking=True)
+                        kind = "fuse on the host"
                 slot.pinned("rows", rows).copy_(rows, non_blocking=True)
                 slot.pinned("count", count).copy_(count, non_blocking=True)
+                if support is not None:
+                    slot.pinned("support", support).copy_(support, non_blocking=True)
             else:
                 slot.pinned("dets", dets).copy_(dets, non_blocking=True)
             slot.done.record()
         except Exception:
             self.free_slots.append(slot)
             raise
-        self.queue.append((slot, tag, inputs.shape[0], geom is not None))
+        self.queue.append((slot, tag, inputs.shape[0], kind))
+
+    def _check_fuse(self, inputs, geom):
+        if self.fuse is None:
+            return
+        if geom is None:
+            raise ValueError("InferenceEngine(fuse=...): every batch must come with geom")
+        if self.fuse[1] and not is_raw_batch(inputs):
+            raise ValueError("tester.flip_tta mirrors raw frames (dataset.device_aug / the Detector); prepared float32 images cannot be mirrored")
 
     def _run_on_host(self, inputs, calibs, img_size, height_crop, prep, geom, tag):
         if geom is not None and self.decode is None:
             raise ValueError("a batch with geometry needs InferenceEngine(decode=(cls_mean_size, threshold))")
+        self._check_fuse(inputs, geom)
         images = prepare(inputs, prep, self.device) if is_raw_batch(inputs) else inputs.to(self.device)
         img_sizes = self._img_sizes(img_size, height_crop)
+        flip = self.fuse is not None and self.fuse[1]
+        if flip:
+            mirrored = prep.clone()
+            mirrored[:, 8] = prep[:, 8] + 1 - 2 * torch.remainder(prep[:, 8], 2)
+            images = torch.cat([images, prepare(inputs, mirrored, self.device)])
+            calibs, img_sizes, geom = torch.cat([calibs, calibs]), torch.cat([img_sizes, img_sizes]), torch.cat([geom, geom])
         t0 = time.time()
         with torch.no_grad():
             outputs = self.model(images, calibs.to(self.device), None, img_sizes, dn_args=0)
         self.model_seconds += time.time() - t0
-        self.images += images.shape[0]
+        self.images += inputs.shape[0]
         self.eager_forwards += 1
         dets = extract_dets_from_outputs(outputs=outputs, K=self.max_objs, topk=self.topk).cpu().numpy()
         if geom is None:
             return Completed(tag, dets=dets)
         rows, count = decode_rows_host(dets, geom.numpy(), self.decode[0].numpy(), self.decode[1])
-        return Completed(tag, rows=rows, count=count)
+        if self.fuse is None:
+            return Completed(tag, rows=rows, count=count)
+        rows, count, support = fuse_rows_host(rows, count, geom.numpy()[:inputs.shape[0]], self.fuse[0], self.fuse[2], 2 if flip else 1)
+        return Completed(tag, rows=rows, count=count, support=support)
 
 
 class _Camera:
