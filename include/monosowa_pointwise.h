@@ -302,6 +302,33 @@ int mono_focal_weighted_bwd_f32(const float *logits, const long long *idx, const
                                 const float *grad_out, float *grad_logits, int NL, int B, int Q, int C, int K, float alpha, float gamma,
                                 void *stream);
 
+/* Ignore regions (model.ignore_ioa): queries that sit on an object known to exist that is no target are not trained as background.
+ * boxes [NL, B, Q, 6] (cx, cy, l, r, t, b); ignore_boxes [B, M, 4] (x1, y1, x2, y2, normalised) with ignore_mask [B, M] bytes.
+ * flags [NL, B, Q] bytes: 1 when, with p = (cx - l, cy - t, cx + r, cy + b) and A = (p.x2 - p.x1)(p.y2 - p.y1), some box g of the
+ * cell's image with a set mask byte has A > 0, iw = min(p.x2, g.x2) - max(p.x1, g.x1) > 0, ih (the same in y) > 0 and
+ * iw ih >= ioa A: intersection over the QUERY's area.  float32, every operation rounded on its own (no contraction), min / max hand
+ * NaNs on, so a NaN anywhere leaves the flag 0.  counts [NL] int32: the flagged cells of every layer.  One launch (one workgroup per
+ * layer), no atomics, nothing has to be zeroed; it knows nothing of the matching.
+ * Returns -1 for a NULL pointer, -2 for NL, B, Q or M < 1. */
+int mono_ignore_flags_f32(const float *boxes, const float *ignore_boxes, const unsigned char *ignore_mask, unsigned char *flags,
+                          int *counts, int NL, int B, int Q, int M, float ioa, void *stream);
+/* The four focal entry points above with those flag bytes (`ignore` [NL, B, Q]): a cell that no pair of idx claims and whose byte is
+ * set adds none of its C terms to the focal sum (skipped, not multiplied by 0: its logits may be non-finite) and its row of
+ * grad_logits is +0.0; a flagged cell that is matched keeps its terms.  class_error and cardinality_error count every cell.  All
+ * bytes 0: the bytes of the entry points above.  Limits and error codes are the siblings'; a NULL `ignore` returns -1. */
+int mono_focal_ignore_fwd_f32(const float *logits, const long long *idx, const long long *labels, const float *sizes,
+                              const unsigned char *ignore, float *out, int NL, int B, int Q, int C, int K, float alpha, float gamma,
+                              void *stream);
+int mono_focal_ignore_bwd_f32(const float *logits, const long long *idx, const long long *labels, const unsigned char *ignore,
+                              const float *grad_out, float *grad_logits, int NL, int B, int Q, int C, int K, float alpha, float gamma,
+                              void *stream);
+int mono_focal_weighted_ignore_fwd_f32(const float *logits, const long long *idx, const long long *labels, const float *sizes,
+                                       const float *t_weight, const unsigned char *ignore, float *out, int NL, int B, int Q, int C,
+                                       int K, float alpha, float gamma, void *stream);
+int mono_focal_weighted_ignore_bwd_f32(const float *logits, const long long *idx, const long long *labels, const float *t_weight,
+                                       const unsigned char *ignore, const float *grad_out, float *grad_logits, int NL, int B, int Q,
+                                       int C, int K, float alpha, float gamma, void *stream);
+
 /* Label audit (monosowa_amd/label_audit.py): what the matched-pair terms above say about every single LABEL.  The predictions and idx
  * [3, NL, K] are those of mono_matched_losses_fwd_f32 and mono_focal_fwd_f32; labels [T] int64.  out: [T, 9] float64; row t covers the
  * pairs k of layer `layer` with idx[2][layer][k] == t:

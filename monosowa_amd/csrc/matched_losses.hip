@@ -348,8 +348,12 @@ __device__ __forceinline__ void focal_factors(float x, bool t, float alpha, floa
   wmod = w * (gamma == 2.f ? q * q : powf(q, gamma));
 }
 
-template <bool W>
-__global__ __launch_bounds__(kFocalThreads) void focal_fwd_kernel(const FocalArgs a, const float *__restrict__ tw, float *__restrict__ out) {
+// I (ignore regions): a cell that no pair claimed (LDS class C) and whose byte of ign [NL, B, Q] is set adds none of its C terms: the
+// terms are evaluated like the sibling's, fma for fma, and the running sum is kept by a select, so a non-finite logit of such a cell
+// never reaches it and every other cell adds the sibling's bits.  The two logging entries count every cell, as before.
+template <bool W, bool I = false>
+__global__ __launch_bounds__(kFocalThreads) void focal_fwd_kernel(const FocalArgs a, const float *__restrict__ tw, float *__restrict__ out,
+                                                                  const unsigned char *__restrict__ ign = nullptr) {
   __shared__ unsigned char cls[W ? kFocalWeightedMaxCells : kFocalMaxCells];
   __shared__ unsigned short pair[W ? kFocalWeightedMaxCells : 1];
   __shared__ float red[kFocalThreads / 64];
@@ -364,11 +368,18 @@ __global__ __launch_bounds__(kFocalThreads) void focal_fwd_kernel(const FocalArg
     const int t = cls[i];
     float w = 1.f;
     if constexpr (W) w = focal_cell_weight(a, l, tw, pair[i]);
+    bool skip = false;
+    if constexpr (I) skip = t == a.C && ign[(long long)l * cells + i] != 0;
     int best = 0;
     float bv = lg[(long long)i * a.C];
     for (int c = 0; c < a.C; ++c) {
       const float x = lg[(long long)i * a.C + c];
-      if constexpr (W) {
+      if constexpr (I) {
+        float wmod, ce;
+        focal_factors(x, c == t, a.alpha, a.gamma, wmod, ce);
+        const float with = __builtin_fmaf(wmod * w, ce, sum);
+        sum = skip ? sum : with;
+      } else if constexpr (W) {
         float wmod, ce;
         focal_factors(x, c == t, a.alpha, a.gamma, wmod, ce);
         sum = __builtin_fmaf(wmod * w, ce, sum);
@@ -399,9 +410,13 @@ __global__ __launch_bounds__(kFocalThreads) void focal_fwd_kernel(const FocalArg
 // grad_logits[l, b, q, c] = grad_out[l] * d focal / d logit     (grad_out: gradient of the per-layer focal SUM)
 // W: the unweighted loop, statement for statement, then the C gradients of every matched cell times the weight of its target (see
 // matched_bwd_kernel); the workgroup meets in between, a cell's gradients come from other threads.
-template <bool W>
+// I: the row of an ignored cell (see focal_fwd_kernel) is written as +0.0, whatever its logits hold -- stored over what the unweighted
+// loop left there, in a pass of its own behind it, like the weights: a select inside the loop changed the compiler's contraction of the
+// other rows' expressions, and those are the sibling's bytes.
+template <bool W, bool I = false>
 __global__ __launch_bounds__(kFocalThreads) void focal_bwd_kernel(const FocalArgs a, const float *__restrict__ tw,
-                                                                  const float *__restrict__ grad_out, float *__restrict__ grad_logits) {
+                                                                  const float *__restrict__ grad_out, float *__restrict__ grad_logits,
+                                                                  const unsigned char *__restrict__ ign = nullptr) {
   __shared__ unsigned char cls[kFocalMaxCells];
   const int l = blockIdx.x, cells = a.B * a.Q;
   focal_class_map<false>(a, l, cls, nullptr);
@@ -421,6 +436,14 @@ __global__ __launch_bounds__(kFocalThreads) void focal_bwd_kernel(const FocalArg
       const float w = tw[ti[k]];
       float *row = gl + (bi[k] * a.Q + qi[k]) * a.C;
       for (int c = 0; c < a.C; ++c) row[c] *= w;
+    }
+  }
+  if constexpr (I) {
+    __syncthreads();
+    for (int cell = threadIdx.x; cell < cells; cell += kFocalThreads) {
+      if (cls[cell] != a.C || ign[(long long)l * cells + cell] == 0) continue;
+      float *row = gl + (long long)cell * a.C;
+      for (int c = 0; c < a.C; ++c) row[c] = 0.f;
     }
   }
 }
@@ -501,6 +524,69 @@ __global__ __launch_bounds__(256) void match_cost_kernel(const CostArgs a, float
   c = rn_add(c, rn_mul(a.w_class, cost_class));
   c = rn_add(c, rn_mul(a.w_giou, cost_giou));
   out[i] = c;
+}
+
+// ---- ignore regions: which queries sit on an object that is known to exist and is no target -----------------------------------------
+//   flags[l, b, q] = 1 when for some valid box g of image b, with p = (cx - l, cy - t, cx + r, cy + b) of the predicted box and
+//   A = (p.x2 - p.x1)(p.y2 - p.y1):   A > 0,  iw = min(p.x2, g.x2) - max(p.x1, g.x1) > 0,  ih likewise > 0,  iw ih >= ioa A
+// -- intersection over the QUERY's area.  float32, every operation rounded on its own (rn()), min / max handing NaNs on like
+// torch.minimum / np.minimum, so a NaN anywhere fails the comparisons and a numpy float32 restatement gives the same bytes.  Whether the
+// cell is matched is not known here: the focal kernels look at that.  One workgroup per layer, which also writes the layer's number
+// of flagged cells (LDS tree, no atomics, nothing to zero first); the launch does not depend on the matching.
+constexpr int kIgnoreThreads = 1024;
+
+struct IgnoreArgs {
+  const float *boxes;                  // [NL, B, Q, 6]
+  const float *ign;                    // [B, M, 4] x1, y1, x2, y2
+  const unsigned char *mask;           // [B, M]
+  int NL, B, Q, M;
+  float ioa;
+};
+
+__global__ __launch_bounds__(kIgnoreThreads) void ignore_flags_kernel(const IgnoreArgs a, unsigned char *__restrict__ flags,
+                                                                      int *__restrict__ counts) {
+  __shared__ int red[kIgnoreThreads / 64];
+  const int l = blockIdx.x, cells = a.B * a.Q;
+  auto tmin = [](const float u, const float v) { return (u != u || u < v) ? u : v; };
+  auto tmax = [](const float u, const float v) { return (u != u || u > v) ? u : v; };
+  int n = 0;
+  for (int i = threadIdx.x; i < cells; i += kIgnoreThreads) {
+    const int b = i / a.Q;
+    const float *pb = a.boxes + ((long long)l * cells + i) * 6;
+    const float x1 = rn_sub(pb[0], pb[2]), y1 = rn_sub(pb[1], pb[4]), x2 = rn_add(pb[0], pb[3]), y2 = rn_add(pb[1], pb[5]);
+    const float area = rn_mul(rn_sub(x2, x1), rn_sub(y2, y1));
+    const float need = rn_mul(a.ioa, area);
+    bool hit = false;
+    if (area > 0.f) {
+      const float *g = a.ign + (long long)b * a.M * 4;
+      const unsigned char *m = a.mask + (long long)b * a.M;
+      // the mask bytes eight at a time: one byte load per slot behind a branch each is a chain of 50 load latencies per cell
+      for (int j0 = 0; j0 < a.M; j0 += 8) {
+        unsigned char mm[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) mm[u] = j0 + u < a.M ? m[j0 + u] : (unsigned char)0;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          if (!mm[u]) continue;
+          const int j = j0 + u;
+          const float iw = rn_sub(tmin(x2, g[j * 4 + 2]), tmax(x1, g[j * 4 + 0]));
+          const float ih = rn_sub(tmin(y2, g[j * 4 + 3]), tmax(y1, g[j * 4 + 1]));
+          hit = hit || (iw > 0.f && ih > 0.f && rn_mul(iw, ih) >= need);
+        }
+      }
+    }
+    flags[(long long)l * cells + i] = hit ? 1 : 0;
+    n += hit ? 1 : 0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int tot = 0;
+    for (int w = 0; w < kIgnoreThreads / 64; ++w) tot += red[w];
+    counts[l] = tot;
+  }
 }
 
 }  // namespace mono

@@ -1563,6 +1563,60 @@ int mono_focal_weighted_bwd_f32(const float *logits, const long long *idx, const
   return (int)hipGetLastError();
 }
 
+// ---- ignore regions (matched_losses.hip): the flags, then the four focal entry points above with the flag bytes ------------------
+int mono_ignore_flags_f32(const float *boxes, const float *ignore_boxes, const unsigned char *ignore_mask, unsigned char *flags,
+                          int *counts, int NL, int B, int Q, int M, float ioa, void *stream) {
+  if (!boxes || !ignore_boxes || !ignore_mask || !flags || !counts) return -1;
+  if (NL <= 0 || B <= 0 || Q <= 0 || M <= 0 || (long long)B * Q > (1ll << 30)) return -2;
+  const mono::IgnoreArgs a{boxes, ignore_boxes, ignore_mask, NL, B, Q, M, ioa};
+  mono::ignore_flags_kernel<<<NL, mono::kIgnoreThreads, 0, (hipStream_t)stream>>>(a, flags, counts);
+  return (int)hipGetLastError();
+}
+
+int mono_focal_ignore_fwd_f32(const float *logits, const long long *idx, const long long *labels, const float *sizes,
+                              const unsigned char *ignore, float *out, int NL, int B, int Q, int C, int K, float alpha, float gamma,
+                              void *stream) {
+  if (!logits || !out || !sizes || !ignore || (K > 0 && (!idx || !labels))) return -1;
+  if (NL <= 0 || B <= 0 || Q <= 0 || C <= 0 || C > 255 || K < 0 || B > 256 || (long long)B * Q > mono::kFocalMaxCells) return -2;
+  const mono::FocalArgs a{logits, idx, labels, sizes, NL, B, Q, C, K, alpha, gamma};
+  mono::focal_fwd_kernel<false, true><<<NL, mono::kFocalThreads, 0, (hipStream_t)stream>>>(a, nullptr, out, ignore);
+  return (int)hipGetLastError();
+}
+
+int mono_focal_weighted_ignore_fwd_f32(const float *logits, const long long *idx, const long long *labels, const float *sizes,
+                                       const float *t_weight, const unsigned char *ignore, float *out, int NL, int B, int Q, int C,
+                                       int K, float alpha, float gamma, void *stream) {
+  if (!logits || !out || !sizes || !ignore || (K > 0 && (!idx || !labels || !t_weight))) return -1;
+  if (NL <= 0 || B <= 0 || Q <= 0 || C <= 0 || C > 255 || K < 0 || B > 256 || (long long)B * Q > mono::kFocalWeightedMaxCells ||
+      K >= (int)mono::kFocalNoPair)
+    return -2;
+  const mono::FocalArgs a{logits, idx, labels, sizes, NL, B, Q, C, K, alpha, gamma};
+  mono::focal_fwd_kernel<true, true><<<NL, mono::kFocalThreads, 0, (hipStream_t)stream>>>(a, t_weight, out, ignore);
+  return (int)hipGetLastError();
+}
+
+int mono_focal_ignore_bwd_f32(const float *logits, const long long *idx, const long long *labels, const unsigned char *ignore,
+                              const float *grad_out, float *grad_logits, int NL, int B, int Q, int C, int K, float alpha, float gamma,
+                              void *stream) {
+  if (!logits || !grad_out || !grad_logits || !ignore || (K > 0 && (!idx || !labels))) return -1;
+  if (NL <= 0 || B <= 0 || Q <= 0 || C <= 0 || C > 255 || K < 0 || (long long)B * Q > mono::kFocalMaxCells) return -2;
+  const mono::FocalArgs a{logits, idx, labels, nullptr, NL, B, Q, C, K, alpha, gamma};
+  mono::focal_bwd_kernel<false, true><<<NL, mono::kFocalThreads, 0, (hipStream_t)stream>>>(a, nullptr, grad_out, grad_logits, ignore);
+  return (int)hipGetLastError();
+}
+
+int mono_focal_weighted_ignore_bwd_f32(const float *logits, const long long *idx, const long long *labels, const float *t_weight,
+                                       const unsigned char *ignore, const float *grad_out, float *grad_logits, int NL, int B, int Q,
+                                       int C, int K, float alpha, float gamma, void *stream) {
+  if (!logits || !grad_out || !grad_logits || !ignore || (K > 0 && (!idx || !labels || !t_weight))) return -1;
+  if (NL <= 0 || B <= 0 || Q <= 0 || C <= 0 || C > 255 || K < 0 || (long long)B * Q > mono::kFocalWeightedMaxCells ||
+      K >= (int)mono::kFocalNoPair)
+    return -2;
+  const mono::FocalArgs a{logits, idx, labels, nullptr, NL, B, Q, C, K, alpha, gamma};
+  mono::focal_bwd_kernel<true, true><<<NL, mono::kFocalThreads, 0, (hipStream_t)stream>>>(a, t_weight, grad_out, grad_logits, ignore);
+  return (int)hipGetLastError();
+}
+
 
 // ---- label audit (matched_losses.hip): per flat target the mean terms of its matched pairs of one layer, nine doubles ------------
 int mono_label_audit_f32(const float *logits, const float *boxes, const float *depth, const float *dims, const float *angle,

@@ -45,7 +45,7 @@ import tqdm
 from ..image_prep import is_raw_batch, prepare
 from ..monodetr import misc
 from ..monodetr.criterion import weighted_total
-from ..synthetic import attach_host_mask, attach_host_weight, host_label_weight
+from ..synthetic import attach_host_any, attach_host_mask, attach_host_weight, host_label_weight
 from ..synthetic import prepare_targets as _prepare_targets
 from .save_helper import get_checkpoint_state, load_checkpoint, save_checkpoint, unwrap
 
@@ -93,7 +93,10 @@ def stage_batch(raw, device):
     calibs = calibs.to(device, non_blocking=True)
     host_mask = targets["mask_2d"].numpy() if not targets["mask_2d"].is_cuda else None
     host_weight = targets["label_weight"].numpy() if "label_weight" in targets and not targets["label_weight"].is_cuda else None
+    host_ignore = bool(targets["ignore_mask"].any()) if "ignore_mask" in targets and not targets["ignore_mask"].is_cuda else None
     targets = {k: v.to(device, non_blocking=True) for k, v in targets.items()}
+    if host_ignore is not None:
+        attach_host_any(targets["ignore_mask"], host_ignore)          # a batch without an ignore box is a batch without the keys
     if host_mask is not None:
         attach_host_mask(targets["mask_2d"], host_mask)      # prepare_targets then needs no device sync
     if host_weight is not None:
@@ -521,6 +524,9 @@ class Trainer(object):
         report = self._guard_report()
         if report is not None:
             print("grad_norm: %.4g, skipped: %d\n" % (report["grad_norm"], report["skipped_total"]))
+        ignore = self.detr_loss.ignore_report() if hasattr(self.detr_loss, "ignore_report") else None
+        if ignore is not None:                             # dataset.ignore_regions: queries left out of loss_ce in this step, all layers
+            print("ignored: %d of %d\n" % (sum(ignore[0]), len(ignore[0]) * ignore[1]))
 
     @staticmethod
     def prepare_targets(targets, batch_size):

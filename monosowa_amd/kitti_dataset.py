@@ -20,6 +20,10 @@ a batch of them into the same float32 images with one HIP launch.
 `label_weights` (optional, training splits only; this project's): a weight per label, `targets["label_weight"]` float32 `[50]`, from
 the label file's score column or from a CSV of `(img_id, line, weight)` -- see `KITTI_Dataset.__init__`.
 
+`ignore_regions` (optional, training splits only; this project's): `targets["ignore_boxes"]` float32 `[50, 4]` and
+`targets["ignore_mask"]` bool `[50]`, the 2D boxes of the objects that are known to exist and are no targets -- see
+`KITTI_Dataset.__init__`.
+
 Not carried over (off in both shipped configs and tied to files of the pseudo-label pipeline): `use_add_data` (per-car
 masks / lidar in dill+zstd), `use_depth`, `output_lidar` -- they raise.
 """
@@ -217,8 +221,12 @@ def affine_transform(pt, t):
     return np.dot(t, np.array([pt[0], pt[1], 1.0], dtype=np.float32).T)[:2]
 
 
+IGNORE_CLASSES = ("DontCare", "Van", "Person_sitting")      # default of dataset.ignore_classes: what the KITTI protocol itself ignores
+
+
 class KITTI_Dataset(data.Dataset):
     label_weights = None             # dataset.label_weights: None, 'score' or {(img_id, line): weight}
+    ignore_regions = False           # dataset.ignore_regions: the targets carry ignore_boxes / ignore_mask
 
     def __init__(self, split, cfg):
         self.root_dir = cfg.get("root_dir")
@@ -242,6 +250,21 @@ class KITTI_Dataset(data.Dataset):
                 raise ValueError("dataset.label_weights = %r is neither 'score' nor the path of a CSV file (absent or None: off)" % (source,))
             self.label_weight_default = _check_label_weight(cfg.get("label_weight_default", 1.0), "dataset.label_weight_default")
             self.label_weights = "score" if source == "score" else read_label_weights(source)
+        # dataset.ignore_regions (optional; training splits only): true -- the targets gain ignore_boxes [max_objs, 4] (x1, y1, x2, y2,
+        # normalised, clipped to the image) and ignore_mask [max_objs]: the boxes, in label-line order, of the lines of a class in
+        # dataset.ignore_classes (never one of the writelist), of the writelist lines the loop below drops, and of those it keeps with
+        # mask_2d false.  The criterion leaves unmatched queries on them out of loss_ce (model.ignore_ioa).
+        self.ignore_regions = False
+        flag = cfg.get("ignore_regions") if self.data_augmentation else None
+        if flag is not None:
+            if not isinstance(flag, bool):
+                raise ValueError("dataset.ignore_regions = %r is not a bool (absent, None or false: off)" % (flag,))
+            self.ignore_regions = flag
+        if self.ignore_regions:
+            classes = cfg.get("ignore_classes", list(IGNORE_CLASSES))
+            if isinstance(classes, str) or not all(isinstance(c, str) for c in classes):
+                raise ValueError("dataset.ignore_classes = %r is not a list of class names" % (classes,))
+            self.ignore_classes = [c for c in classes if c not in self.writelist]
 
     @classmethod
     def settings(cls, cfg):
@@ -265,6 +288,9 @@ class KITTI_Dataset(data.Dataset):
         self.meanshape = cfg.get("meanshape", False)
         if cfg.get("class_merging", False):
             self.writelist.extend(["Van", "Truck"])
+            # merged INTO Car: without an id of their own the first Van that passed the filters below raised a KeyError (the
+            # reference's does too, kitti_dataset.py:335)
+            self.cls2id.update({"Van": self.cls2id["Car"], "Truck": self.cls2id["Car"]})
         if cfg.get("use_dontcare", False):
             self.writelist.extend(["DontCare"])
         for key in ("use_add_data", "use_depth", "output_lidar"):
@@ -293,6 +319,23 @@ class KITTI_Dataset(data.Dataset):
 
     def __len__(self):
         return len(self.idx_list)
+
+    def _ignore_boxes(self, objects, trans):
+        """(float32 [max_objs, 4], bool [max_objs]): the (already flipped) 2D boxes of ``objects`` through ``trans`` like a target's
+        ``bbox_2d``, divided by the resolution and clipped to [0, 1]; boxes that are empty after that are dropped, the others packed at
+        the front in the given order, unused slots zero."""
+        out, mask = np.zeros((self.max_objs, 4), dtype=np.float32), np.zeros((self.max_objs,), dtype=bool)
+        k = 0
+        for o in objects:
+            box = o.box2d.copy()
+            box[:2] = affine_transform(box[:2], trans)
+            box[2:] = affine_transform(box[2:], trans)
+            box = np.clip(box / np.tile(self.resolution, 2).astype(np.float32), 0, 1).astype(np.float32)
+            if box[2] <= box[0] or box[3] <= box[1]:
+                continue
+            out[k], mask[k] = box, True
+            k += 1
+        return out, mask
 
     def get_image(self, idx):
         return Image.open(os.path.join(self.image_dir, "%06d.png" % idx))
@@ -403,8 +446,11 @@ class KITTI_Dataset(data.Dataset):
                                                               % (os.path.join(self.label_dir, "%06d.txt" % index), i + 1))
                 elif (index, i) in self.label_weights:
                     label_weight[i] = self.label_weights[(index, i)]
+        ignore_lines = []                           # dataset.ignore_regions: the lines whose boxes become ignore boxes
         for i in range(min(len(objects), n)):
             o = objects[i]
+            if self.ignore_regions and (o.cls_type in self.ignore_classes if o.cls_type not in self.writelist else True):
+                ignore_lines.append(i)              # a writelist line is taken off again below when it ends as a target
             if o.cls_type not in self.writelist or o.level_str == "UnKnown" or o.pos[-1] < 2 or o.pos[-1] > 65:
                 continue
             bbox_2d = o.box2d.copy()
@@ -444,6 +490,8 @@ class KITTI_Dataset(data.Dataset):
             size_3d[i] = src_size_3d[i] - self.cls_mean_size[self.cls2id[o.cls_type]]
             if o.trucation <= 0.5 and o.occlusion <= 2:
                 mask_2d[i] = 1
+                if self.ignore_regions:
+                    ignore_lines.remove(i)
             calibs[i] = calib.P2
             objects_out[i] = np.array([o.h, o.w, o.l, o.pos[0], o.pos[1], o.pos[2], o.ry], dtype=np.float32)
         targets = {"calibs": calibs, "indices": indices, "img_size": img_size, "labels": labels, "boxes": boxes, "boxes_3d": boxes_3d,
@@ -451,6 +499,8 @@ class KITTI_Dataset(data.Dataset):
                    "heading_res": heading_res, "mask_2d": mask_2d, "objects": objects_out}
         if label_weight is not None:
             targets["label_weight"] = label_weight
+        if self.ignore_regions:
+            targets["ignore_boxes"], targets["ignore_mask"] = self._ignore_boxes([objects[i] for i in ignore_lines], trans)
         info.update({"affine": trans, "affine_inv": trans_inv, "scale_depth": crop_scale, "calib_P2": calib.P2, "calib_R0": calib.R0,
                      "calib_V2C": calib.V2C, "resolution": self.resolution, "flip": flipped,
                      "templates_dimensions": np.array([self.template_height, self.template_width, self.template_length], dtype=np.float32)})

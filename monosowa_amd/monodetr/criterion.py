@@ -20,8 +20,8 @@ from torch import nn
 from . import box_ops
 from .losses import DDNLoss, sigmoid_focal_loss
 from .misc import accuracy, get_world_size, is_dist_avail_and_initialized
-from ..pointwise import (focal_classification, focal_classification_supported, focal_classification_weighted_supported, matched_losses,
-                         matched_losses_supported)
+from ..pointwise import (focal_classification, focal_classification_supported, focal_classification_weighted_supported, ignore_flags,
+                         matched_losses, matched_losses_supported)
 
 
 def _paired_giou(a, b):
@@ -67,6 +67,19 @@ def _host_weight_sum(targets):
         raise ValueError("the weighted normaliser is formed on the host: device-resident label_weight needs the weight_sum that "
                          "synthetic.prepare_targets sets from the host copy (synthetic.attach_host_weight)")
     return label_weight_sum(np.concatenate([t["label_weight"].detach().reshape(-1).numpy() for t in targets]))
+
+
+def _ignore_regions(targets):
+    """(ignore boxes [B, M, 4] xyxy normalised, mask [B, M]) that ``synthetic.prepare_targets`` leaves on the ``TargetList`` of a batch
+    with ``ignore_boxes`` in which some image has one; None: nothing below changes."""
+    return getattr(targets, "ignore", None)
+
+
+def check_ignore_ioa(value):
+    """``model.ignore_ioa``: the share of a query box's own area that must lie inside an ignore box, a float in (0, 1]."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (0.0 < float(value) <= 1.0):
+        raise ValueError("model.ignore_ioa = %r is not a number in (0, 1]" % (value,))
+    return float(value)
 
 
 FUSED_FOCAL = True       # classification side (focal sums, class / cardinality errors) as one HIP kernel each way
@@ -177,6 +190,7 @@ class SetCriterion(nn.Module):
     # a monosowa_amd.label_audit.LabelAudit: both formulations hand it the final layer's predictions and matched pairs once the pairs are
     # known (``observe``: one launch, nothing waits); None: nothing is launched, allocated or read for it
     audit = None
+    _ignore_last = None      # what ignore_report reads: the flags, their per-layer counts and the pairs of the last forward with ignore boxes
 
     def __init__(self, num_classes, matcher, weight_dict, focal_alpha, losses, group_num=11, cfg=None,
                  depth_map_size=(80, 24), fast=True):
@@ -196,6 +210,9 @@ class SetCriterion(nn.Module):
         self.use_tfl = bool(cfg["use_tfl"]) if cfg is not None else False
         self.use_mask_loss = bool(cfg["use_mask_loss"]) if cfg is not None else False
         self.mask_loss = cfg["mask_loss"] if cfg is not None else "DICE"
+        # share of a query box's own area inside an ignore box from which an unmatched query is left out of loss_ce; read only when the
+        # targets carry ignore boxes (dataset.ignore_regions)
+        self.ignore_ioa = check_ignore_ioa(cfg.get("ignore_ioa", 0.5) if cfg is not None else 0.5)
         if self.use_tfl or self.use_mask_loss:
             raise NotImplementedError("use_tfl / use_mask_loss need pytorch3d + open3d rendering that the reference "
                                       "itself does not import; they are off in every shipped config")
@@ -228,7 +245,21 @@ class SetCriterion(nn.Module):
         onehot = torch.zeros([src_logits.shape[0], src_logits.shape[1], src_logits.shape[2] + 1],
                              dtype=src_logits.dtype, device=src_logits.device)
         onehot.scatter_(2, target_classes.unsqueeze(-1), 1)
-        if _has_label_weight(targets):              # the C terms of a matched query times its label's weight, 1 elsewhere
+        regions = _ignore_regions(targets)
+        if regions is not None:                     # unmatched queries on an ignore box: none of their C terms, no gradient
+            flags, counts = ignore_flags(outputs["pred_boxes"].detach().unsqueeze(0), regions[0], regions[1], self.ignore_ioa)
+            ignored = (flags[0].bool() & (target_classes == self.num_classes)).unsqueeze(-1)
+            if self._ignore_last is None or "layers" not in self._ignore_last:
+                self._ignore_last = {"layers": []}
+            self._ignore_last["layers"].append((flags[0], counts, idx))
+            cell_w = None
+            if _has_label_weight(targets):
+                cell_w = torch.ones(src_logits.shape[:2], dtype=src_logits.dtype, device=src_logits.device)
+                cell_w[idx] = self._matched(targets, indices, "label_weight").to(src_logits.dtype)
+                cell_w = cell_w.unsqueeze(-1)
+            loss_ce = sigmoid_focal_loss(src_logits, onehot[:, :, :-1], num_boxes, alpha=self.focal_alpha, gamma=2, weight=cell_w,
+                                         ignore=ignored) * src_logits.shape[1]
+        elif _has_label_weight(targets):            # the C terms of a matched query times its label's weight, 1 elsewhere
             cell_w = torch.ones(src_logits.shape[:2], dtype=src_logits.dtype, device=src_logits.device)
             cell_w[idx] = self._matched(targets, indices, "label_weight").to(src_logits.dtype)
             loss_ce = sigmoid_focal_loss(src_logits, onehot[:, :, :-1], num_boxes, alpha=self.focal_alpha, gamma=2,
@@ -337,6 +368,8 @@ class SetCriterion(nn.Module):
     def forward(self, outputs, targets, mask_dict=None, info=None, num_boxes=None):
         """``num_boxes`` (a float or a 0-d device tensor): the normaliser to use in place of this forward's own box count, already
         job-wide -- nothing is all-reduced then.  The Trainer's gradient accumulation passes the cycle-wide count."""
+        if _ignore_regions(targets) is None:
+            self._ignore_last = None
         if self.fast:
             return self.forward_fast(outputs, targets, num_boxes)
         return self.forward_layerwise(outputs, targets, mask_dict, info, num_boxes)
@@ -405,6 +438,11 @@ class SetCriterion(nn.Module):
             loss_depth_map = self.ddn_loss.forward_padded(outputs["pred_depth_map_logits"], boxes2d, depth2d, valid_t, box_weight=weight2d)
         else:
             loss_depth_map = self.ddn_loss.forward_padded(outputs["pred_depth_map_logits"], boxes2d, depth2d, valid_t)
+        # ignore regions: which queries sit on an ignore box does not depend on the matching either -- one launch, here
+        regions = _ignore_regions(targets)
+        flags = None
+        if regions is not None:
+            flags, flag_counts = ignore_flags(boxes.detach(), regions[0], regions[1], self.ignore_ioa)
 
         # everything the fused tail needs that does not depend on the assignment is made ready BEFORE the wait: behind it the
         # GPU queue is empty and every microsecond of host time is step time (measured: 1.05 ms from indices to total)
@@ -433,10 +471,15 @@ class SetCriterion(nn.Module):
             with torch.no_grad():
                 self.audit.observe(*[t.detach() for t in (prep if fused_tail else (logits, boxes, depth, dims, angle))], idx,
                                    dict(flat, labels=labels64) if fused_tail else flat, layer=0)
+        if flags is not None:
+            self._ignore_last = {"flags": flags, "counts": flag_counts, "idx": idx}
         if weighted and fused_tail and K > 0 and focal_classification_weighted_supported(logits, idx):
             # the same four launches through the weighted entry points
-            from ..pointwise import _FocalClassificationWeighted, _MatchedLossesWeighted
-            cls3 = _FocalClassificationWeighted.apply(prep[0], idx, labels64, sizes_dev, weight32, float(self.focal_alpha), 2.0)
+            from ..pointwise import _FocalClassificationIgnore, _FocalClassificationWeighted, _MatchedLossesWeighted
+            if flags is not None:
+                cls3 = _FocalClassificationIgnore.apply(prep[0], idx, labels64, sizes_dev, weight32, flags, float(self.focal_alpha), 2.0)
+            else:
+                cls3 = _FocalClassificationWeighted.apply(prep[0], idx, labels64, sizes_dev, weight32, float(self.focal_alpha), 2.0)
             sums = _MatchedLossesWeighted.apply(prep[1], prep[2], prep[3], prep[4], idx, *prep_t, weight32)
             mat = torch.cat([cls3, sums], 1).t() * scale_col                     # [9, NL]
             keys = ("loss_ce", "class_error", "cardinality_error", "loss_center", "loss_bbox", "loss_giou", "loss_depth", "loss_dim",
@@ -445,8 +488,11 @@ class SetCriterion(nn.Module):
         if not weighted and fused_tail and K > 0 and focal_classification_supported(logits, idx):
             # the whole criterion behind the matching in four launches: classification side + matched-pair losses, forward
             # and backward (csrc/matched_losses.hip), the loss matrix in two more
-            from ..pointwise import _FocalClassification, _MatchedLosses
-            cls3 = _FocalClassification.apply(prep[0], idx, labels64, sizes_dev, float(self.focal_alpha), 2.0)
+            from ..pointwise import _FocalClassification, _FocalClassificationIgnore, _MatchedLosses
+            if flags is not None:
+                cls3 = _FocalClassificationIgnore.apply(prep[0], idx, labels64, sizes_dev, None, flags, float(self.focal_alpha), 2.0)
+            else:
+                cls3 = _FocalClassification.apply(prep[0], idx, labels64, sizes_dev, float(self.focal_alpha), 2.0)
             sums = _MatchedLosses.apply(prep[1], prep[2], prep[3], prep[4], idx, *prep_t)
             mat = torch.cat([cls3, sums], 1).t() * scale_col                     # [9, NL]
             keys = ("loss_ce", "class_error", "cardinality_error", "loss_center", "loss_bbox", "loss_giou", "loss_depth", "loss_dim",
@@ -462,8 +508,12 @@ class SetCriterion(nn.Module):
         target_classes = torch.full((NL, B, Q), self.num_classes, dtype=torch.int64, device=dev)
         target_classes[l_idx, b_idx, q_idx] = tgt_cls
         onehot = torch.zeros((NL, B, Q, C + 1), dtype=logits.dtype, device=dev).scatter_(3, target_classes.unsqueeze(-1), 1)[..., :-1]
-        prob = logits.sigmoid()
-        ce = F.binary_cross_entropy_with_logits(logits, onehot, reduction="none")
+        cls_logits = logits
+        if flags is not None:                       # an ignored cell: selected away on both sides, its logits reach nothing
+            ignored = (flags.bool() & (target_classes == self.num_classes)).unsqueeze(-1)
+            cls_logits = torch.where(ignored, logits.new_zeros(()), logits)
+        prob = cls_logits.sigmoid()
+        ce = F.binary_cross_entropy_with_logits(cls_logits, onehot, reduction="none")
         p_t = prob * onehot + (1 - prob) * (1 - onehot)
         focal = ce * ((1 - p_t) ** 2)
         if self.focal_alpha >= 0:
@@ -474,6 +524,8 @@ class SetCriterion(nn.Module):
             cell_w = torch.ones((NL, B, Q), dtype=logits.dtype, device=dev)
             cell_w[l_idx, b_idx, q_idx] = pair_w
             focal = focal * cell_w.unsqueeze(-1)
+        if flags is not None:
+            focal = torch.where(ignored, focal.new_zeros(()), focal)
         per_layer["loss_ce"] = focal.mean(2).sum((1, 2)) / num_boxes * Q
         matched_logits = take(logits)
         if K:
@@ -524,6 +576,24 @@ class SetCriterion(nn.Module):
 
         return self._finish(per_layer, NL, dev, loss_depth_map)
 
+    def ignore_report(self):
+        """(ignored, cells) of the last forward whose targets carried ignore boxes: per layer (the final one first) the number of
+        queries that were flagged by ``ignore_flags`` AND unmatched, i.e. left out of loss_ce, and the number of queries B * Q of a
+        layer.  Reads the device (a synchronisation); None before the first such forward."""
+        rec = self._ignore_last
+        if rec is None:
+            return None
+        if "layers" in rec:
+            if not rec["layers"]:
+                return None
+            ignored = [int(c.sum()) - int(f[i].sum()) for f, c, i in rec["layers"]]
+            return ignored, int(rec["layers"][0][0].numel())
+        flags, counts, idx = rec["flags"], rec["counts"], rec["idx"]
+        NL, K = idx.shape[1:]
+        matched = flags[torch.arange(NL, device=flags.device).view(NL, 1).expand(NL, K), idx[0], idx[1]].sum(1, dtype=torch.int64)
+        ignored = (counts.to(torch.int64) - matched).tolist()
+        return [int(v) for v in ignored], int(flags[0].numel())
+
     @staticmethod
     def _finish(per_layer, NL, dev, loss_depth_map, mat=None):
         losses = LossDict()
@@ -562,6 +632,8 @@ class SetCriterion(nn.Module):
     def forward_layerwise(self, outputs, targets, mask_dict=None, info=None, num_boxes=None):
         outputs_without_aux = {k: v for k, v in outputs.items() if k != "aux_outputs"}
         group_num = self.group_num if self.training else 1
+        if _ignore_regions(targets) is not None:
+            self._ignore_last = {"layers": []}
         indices = self.matcher(outputs_without_aux, targets, group_num=group_num)
         if self.audit is not None:
             self._observe_layerwise(outputs_without_aux, targets, indices)

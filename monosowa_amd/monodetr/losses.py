@@ -16,8 +16,12 @@ import torch.nn.functional as F
 from torch import nn
 
 
-def sigmoid_focal_loss(inputs, targets, num_boxes, alpha: float = 0.25, gamma: float = 2, weight=None):
-    """``weight`` (broadcast against ``inputs``, e.g. [B, Q, 1]): a factor per term, the per-label weights of the matched queries."""
+def sigmoid_focal_loss(inputs, targets, num_boxes, alpha: float = 0.25, gamma: float = 2, weight=None, ignore=None):
+    """``weight`` (broadcast against ``inputs``, e.g. [B, Q, 1]): a factor per term, the per-label weights of the matched queries.
+    ``ignore`` (bool, broadcast against ``inputs``, e.g. [B, Q, 1]): terms that are left out -- selected away, not multiplied by 0, on
+    both sides of the expression, so that a non-finite logit there reaches neither the loss nor a gradient."""
+    if ignore is not None:
+        inputs = torch.where(ignore, inputs.new_zeros(()), inputs)
     prob = inputs.sigmoid()
     ce = F.binary_cross_entropy_with_logits(inputs, targets, reduction="none")
     p_t = prob * targets + (1 - prob) * (1 - targets)
@@ -26,6 +30,8 @@ def sigmoid_focal_loss(inputs, targets, num_boxes, alpha: float = 0.25, gamma: f
         loss = (alpha * targets + (1 - alpha) * (1 - targets)) * loss
     if weight is not None:
         loss = loss * weight
+    if ignore is not None:
+        loss = torch.where(ignore, loss.new_zeros(()), loss)
     return loss.mean(1).sum() / num_boxes
 
 

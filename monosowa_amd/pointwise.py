@@ -17,7 +17,9 @@ SYMBOLS = ("mono_bias_act_f32", "mono_bias_relu_maxpool_nhwc_f32", "mono_conv1x1
            "mono_linear_wgrad_workspace", "mono_linear_wgrad_f32", "mono_colsum_levels_blocks", "mono_colsum_levels_f32", "mono_relu_grad_scale_f32",
            "mono_set_deterministic", "mono_groupnorm_stats_doubles", "mono_groupnorm_part_doubles", "mono_grad_accumulate_f32", "mono_ema_update_f32", "mono_step_stats_f32",
            "mono_label_audit_f32", "mono_matched_losses_weighted_fwd_f32", "mono_matched_losses_weighted_bwd_f32", "mono_focal_weighted_fwd_f32",
-           "mono_focal_weighted_bwd_f32", "mono_ddn_loss_weighted_fwd_f32", "mono_ddn_loss_weighted_bwd_f32", "mono_focal_weighted_max_cells")
+           "mono_focal_weighted_bwd_f32", "mono_ddn_loss_weighted_fwd_f32", "mono_ddn_loss_weighted_bwd_f32", "mono_focal_weighted_max_cells",
+           "mono_ignore_flags_f32", "mono_focal_ignore_fwd_f32", "mono_focal_ignore_bwd_f32", "mono_focal_weighted_ignore_fwd_f32",
+           "mono_focal_weighted_ignore_bwd_f32")
 _lib = None
 
 
@@ -152,6 +154,12 @@ def load():
         lib.mono_focal_weighted_fwd_f32.argtypes = [P] * 6 + [I] * 5 + [F, F, P]
         lib.mono_focal_weighted_bwd_f32.restype = I
         lib.mono_focal_weighted_bwd_f32.argtypes = [P] * 6 + [I] * 5 + [F, F, P]
+        lib.mono_ignore_flags_f32.restype = I
+        lib.mono_ignore_flags_f32.argtypes = [P] * 5 + [I] * 4 + [F, P]
+        for name, n_ptr in (("mono_focal_ignore_fwd_f32", 6), ("mono_focal_ignore_bwd_f32", 6), ("mono_focal_weighted_ignore_fwd_f32", 7),
+                            ("mono_focal_weighted_ignore_bwd_f32", 7)):
+            getattr(lib, name).restype = I
+            getattr(lib, name).argtypes = [P] * n_ptr + [I] * 5 + [F, F, P]
         lib.mono_ddn_loss_weighted_fwd_f32.restype = I
         lib.mono_ddn_loss_weighted_fwd_f32.argtypes = [P] * 6 + [I] * 5 + [LL] * 3 + [F] * 6 + [P]
         lib.mono_ddn_loss_weighted_bwd_f32.restype = I
@@ -1396,6 +1404,94 @@ class _FocalClassificationWeighted(torch.autograd.Function):
         return grad, None, None, None, None, None, None
 
 
+class _FocalClassificationIgnore(torch.autograd.Function):
+    """``_FocalClassification`` / ``_FocalClassificationWeighted`` (``t_weight`` None or [T]) with the flag bytes ``ignore`` [NL, B, Q]
+    of ``ignore_flags`` (``mono_focal_ignore_*``, ``mono_focal_weighted_ignore_*``): a flagged cell that no pair claims adds nothing to
+    the focal sum and gets a zero gradient row."""
+    @staticmethod
+    def forward(ctx, logits, idx, labels, sizes, t_weight, ignore, alpha, gamma):
+        NL, B, Q, C = logits.shape
+        K = idx.size(2)
+        out = torch.empty((NL, 3), dtype=torch.float32, device=logits.device)
+        with on_device(logits.device):
+            if t_weight is None:
+                name = "mono_focal_ignore_fwd_f32"
+                code = load().mono_focal_ignore_fwd_f32(logits.data_ptr(), idx.data_ptr(), labels.data_ptr(), sizes.data_ptr(),
+                                                        ignore.data_ptr(), out.data_ptr(), NL, B, Q, C, K, alpha, gamma, raw_stream())
+            else:
+                name = "mono_focal_weighted_ignore_fwd_f32"
+                code = load().mono_focal_weighted_ignore_fwd_f32(logits.data_ptr(), idx.data_ptr(), labels.data_ptr(), sizes.data_ptr(),
+                                                                 t_weight.data_ptr(), ignore.data_ptr(), out.data_ptr(), NL, B, Q, C, K,
+                                                                 alpha, gamma, raw_stream())
+        if code:
+            raise RuntimeError("%s failed with code %d" % (name, code))
+        ctx.save_for_backward(logits, idx, labels, ignore, *(() if t_weight is None else (t_weight,)))
+        ctx.consts = (alpha, gamma)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        logits, idx, labels, ignore = ctx.saved_tensors[:4]
+        t_weight = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        NL, B, Q, C = logits.shape
+        g = go[:, 0].contiguous()                       # class / cardinality errors carry no gradient
+        grad = torch.empty_like(logits)
+        with on_device(logits.device):
+            if t_weight is None:
+                name = "mono_focal_ignore_bwd_f32"
+                code = load().mono_focal_ignore_bwd_f32(logits.data_ptr(), idx.data_ptr(), labels.data_ptr(), ignore.data_ptr(),
+                                                        g.data_ptr(), grad.data_ptr(), NL, B, Q, C, idx.size(2), *ctx.consts, raw_stream())
+            else:
+                name = "mono_focal_weighted_ignore_bwd_f32"
+                code = load().mono_focal_weighted_ignore_bwd_f32(logits.data_ptr(), idx.data_ptr(), labels.data_ptr(), t_weight.data_ptr(),
+                                                                 ignore.data_ptr(), g.data_ptr(), grad.data_ptr(), NL, B, Q, C,
+                                                                 idx.size(2), *ctx.consts, raw_stream())
+        if code:
+            raise RuntimeError("%s failed with code %d" % (name, code))
+        return grad, None, None, None, None, None, None, None
+
+
+def ignore_flags_torch(boxes, ignore_boxes, ignore_mask, ioa):
+    """The flags of ``ignore_flags`` from torch operations, each float32 operation rounded on its own: bool [NL, B, Q]."""
+    p = boxes.detach().to(torch.float32)
+    g = ignore_boxes.to(torch.float32)[None, :, None]                              # [1, B, 1, M, 4]
+    x1, y1 = (p[..., 0] - p[..., 2]).unsqueeze(-1), (p[..., 1] - p[..., 4]).unsqueeze(-1)
+    x2, y2 = (p[..., 0] + p[..., 3]).unsqueeze(-1), (p[..., 1] + p[..., 5]).unsqueeze(-1)
+    area = (x2 - x1) * (y2 - y1)
+    iw = torch.minimum(x2, g[..., 2]) - torch.maximum(x1, g[..., 0])
+    ih = torch.minimum(y2, g[..., 3]) - torch.maximum(y1, g[..., 1])
+    need = torch.as_tensor(ioa, dtype=torch.float32, device=p.device) * area
+    hit = (area > 0) & (iw > 0) & (ih > 0) & (iw * ih >= need) & ignore_mask.to(torch.bool)[None, :, None]
+    return hit.any(-1)
+
+
+def ignore_flags_supported(boxes):
+    return boxes.is_cuda and boxes.dtype == torch.float32 and boxes.dim() == 4 and boxes.shape[-1] == 6
+
+
+@torch.no_grad()
+def ignore_flags(boxes, ignore_boxes, ignore_mask, ioa):
+    """-> (flags uint8 [NL, B, Q], counts int32 [NL]): which predicted boxes [NL, B, Q, 6] (cx, cy, l, r, t, b) lie with at least ``ioa``
+    of their own area inside a valid ignore box [B, M, 4] (x1, y1, x2, y2) of their image, and how many per layer
+    (``mono_ignore_flags_f32``: one launch, nothing waits).  On CPU tensors or another dtype: the same float32 arithmetic in torch."""
+    NL, B, Q = boxes.shape[:3]
+    M = ignore_boxes.shape[1]
+    if not ignore_flags_supported(boxes) or M == 0:
+        flags = ignore_flags_torch(boxes, ignore_boxes, ignore_mask, ioa).to(torch.uint8)
+        return flags, flags.sum((1, 2), dtype=torch.int32)
+    boxes = boxes.detach().contiguous()
+    gb = ignore_boxes.to(torch.float32).contiguous()
+    gm = ignore_mask.to(torch.uint8).contiguous() if ignore_mask.dtype != torch.bool else ignore_mask.contiguous().view(torch.uint8)
+    flags = torch.empty((NL, B, Q), dtype=torch.uint8, device=boxes.device)
+    counts = torch.empty((NL,), dtype=torch.int32, device=boxes.device)
+    with on_device(boxes.device):
+        code = load().mono_ignore_flags_f32(boxes.data_ptr(), gb.data_ptr(), gm.data_ptr(), flags.data_ptr(), counts.data_ptr(),
+                                            NL, B, Q, M, float(ioa), raw_stream())
+    if code:
+        raise RuntimeError("mono_ignore_flags_f32 failed with code %d" % code)
+    return flags, counts
+
+
 def focal_classification_supported(logits, idx):
     NL, B, Q, C = logits.shape
     return logits.is_cuda and logits.dtype == torch.float32 and C <= 255 and B <= 256 and B * Q <= 32768 and idx.size(2) > 0
@@ -1410,10 +1506,17 @@ def focal_classification_weighted_supported(logits, idx):
         and 0 < idx.size(2) < 65535
 
 
-def focal_classification(logits, idx, labels, sizes, alpha, gamma=2.0, weight=None):
+def focal_classification(logits, idx, labels, sizes, alpha, gamma=2.0, weight=None, ignore=None):
     """-> [NL, 3]: per decoder layer the sigmoid-focal-loss SUM against the matched one-hot targets (differentiable), the
     class error in % and the cardinality error (monodetr.py:396-449) -- one HIP launch each way.  ``weight`` [T]: the terms of a
-    matched cell times the weight of its target (the weighted kernels); None: the unweighted launches."""
+    matched cell times the weight of its target (the weighted kernels); None: the unweighted launches.  ``ignore`` [NL, B, Q] uint8
+    (``ignore_flags``): flagged cells that no pair claims leave the sum and get no gradient (the ignore entry points); None: the
+    launches without it."""
+    if ignore is not None:
+        return _FocalClassificationIgnore.apply(logits.contiguous(), idx.contiguous(), labels.to(torch.int64).contiguous(),
+                                                sizes.to(torch.float32).contiguous(),
+                                                None if weight is None else weight.reshape(-1).to(torch.float32).contiguous(),
+                                                ignore.to(torch.uint8).contiguous(), float(alpha), float(gamma))
     if weight is not None:
         return _FocalClassificationWeighted.apply(logits.contiguous(), idx.contiguous(), labels.to(torch.int64).contiguous(),
                                                   sizes.to(torch.float32).contiguous(), weight.reshape(-1).to(torch.float32).contiguous(),

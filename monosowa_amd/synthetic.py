@@ -122,6 +122,13 @@ def attach_host_weight(weight_device, weight_host):
     return weight_device
 
 
+def attach_host_any(mask_device, any_host):
+    """Whether the batch has an ignore box at all, known on the host before the batch is shipped: ``prepare_targets`` drops the ignore
+    keys of a batch without one, without a device->host sync."""
+    mask_device._host_any = bool(any_host)
+    return mask_device
+
+
 def host_label_weight(targets):
     """The host copy of ``targets["label_weight"]`` ([B, max_objs] float32): the tensor itself when it lives on the host, else what
     ``attach_host_weight`` left beside it; a device-resident batch without one is refused (nothing here may wait for the device)."""
@@ -140,7 +147,8 @@ def prepare_targets(targets, batch_size):
     The reference indexes every key of every image with a boolean mask (8 x B device->host syncs); here the
     mask is resolved once and each key is gathered once for the whole batch, then split into views.
     With ``label_weight`` in the dict (dataset.label_weights) it is gathered like the other keys and ``weight_sum`` holds the sum of
-    the valid labels' weights, formed on the host."""
+    the valid labels' weights, formed on the host.  With ``ignore_boxes`` / ``ignore_mask`` (dataset.ignore_regions) ``ignore`` holds
+    the two batch-wise, as they are; a batch the host knows to have no ignore box (``attach_host_any``) leaves it None."""
     keys = ("labels", "boxes", "calibs", "depth", "size_3d", "heading_bin", "heading_res", "boxes_3d", "label_weight")
     host = getattr(targets["mask_2d"], "_host_mask", None)
     if host is not None and USE_HOST_MASK:
@@ -157,6 +165,13 @@ def prepare_targets(targets, batch_size):
     per_key = {k: v.split(counts) for k, v in flat.items()}
     out = TargetList({k: per_key[k][b] for k in per_key} for b in range(batch_size))
     out.flat = flat                 # the per-image entries are views of these: the criterion need not concatenate them again
+    if "ignore_boxes" in targets:
+        mask = targets["ignore_mask"]
+        some = getattr(mask, "_host_any", None)
+        if some is None:
+            some = True if mask.is_cuda else bool(mask[:batch_size].any())
+        if some:
+            out.ignore = (targets["ignore_boxes"][:batch_size], mask[:batch_size])
     if "label_weight" in targets:
         from .monodetr.criterion import label_weight_sum
         if host is None or not USE_HOST_MASK:
@@ -172,3 +187,4 @@ class TargetList(list):
     """The reference's list of per-image target dicts, remembering the batch-flat tensors its entries are views of."""
     flat = None
     weight_sum = None      # host float: sum of the valid labels' weights when the batch carries label_weight
+    ignore = None          # (ignore_boxes [B, max_objs, 4], ignore_mask [B, max_objs]) of a batch with dataset.ignore_regions and a box
