@@ -271,6 +271,37 @@ int mono_ddn_loss_weighted_bwd_f32(const float *logits, const float *boxes, cons
                                    const float *box_weight, const float *grad_total, float *grad_logits, int B, int C, int H, int W,
                                    int N, long long sb, long long sc, long long sp, float alpha, float gamma, float fg_weight,
                                    float bg_weight, float depth_min, float depth_max, void *stream);
+/* The four above with ignore regions: ign_boxes [B, M, 4] float32 x1, y1, x2, y2 in depth-map pixels (the normalised boxes times
+ * (W, H, W, H) in float32, one rounding per coordinate), ign_valid [B, M] bytes.  Pixel (y, x) of image b is IGNORED when both hold:
+ *   - no valid target box covers it under the rule above (it is not foreground);
+ *   - some valid ignore box g has x >= floorf(g.x1), x < ceilf(g.x2), y >= floorf(g.y1) and y < ceilf(g.y2).
+ * Each comparison is made in float32 on the floats themselves: a NaN coordinate covers nothing and no float is converted to an
+ * integer.  The rounding is outward like a target box's, WITHOUT the slice wrap of a negative start: an ignore box with x1 = -3.5
+ * covers from column 0 (a target box with these coordinates wraps and is empty).  Foreground wins: a pixel under both keeps its term
+ * and its weight, fg_weight * 0 of a label of weight 0 included.
+ * An ignored pixel contributes none of its C bin terms -- skipped, not multiplied by 0: a non-finite logit there reaches neither the
+ * loss nor a gradient -- and its C logit gradients are written as +0.0.  The divisor stays B H W.  The painted depth, the bins, the
+ * weights and the gradient rows of every other pixel are the sibling entry point's.
+ * forward: ign_count [mono_ddn_loss_blocks(B, H, W)] int32 = the ignored live pixels of each block, once per pixel, reduced like the
+ * loss (no atomics).  NULL pointer: -1; M <= 0 or N <= 0: -2; nothing is written on an error. */
+int mono_ddn_loss_ignore_fwd_f32(const float *logits, const float *boxes, const float *depth, const unsigned char *valid,
+                                 const float *ign_boxes, const unsigned char *ign_valid, float *partial, int *ign_count, int B, int C,
+                                 int H, int W, int N, int M, long long sb, long long sc, long long sp, float alpha, float gamma,
+                                 float fg_weight, float bg_weight, float depth_min, float depth_max, void *stream);
+int mono_ddn_loss_ignore_bwd_f32(const float *logits, const float *boxes, const float *depth, const unsigned char *valid,
+                                 const float *ign_boxes, const unsigned char *ign_valid, const float *grad_total, float *grad_logits,
+                                 int B, int C, int H, int W, int N, int M, long long sb, long long sc, long long sp, float alpha,
+                                 float gamma, float fg_weight, float bg_weight, float depth_min, float depth_max, void *stream);
+int mono_ddn_loss_weighted_ignore_fwd_f32(const float *logits, const float *boxes, const float *depth, const unsigned char *valid,
+                                          const float *box_weight, const float *ign_boxes, const unsigned char *ign_valid,
+                                          float *partial, int *ign_count, int B, int C, int H, int W, int N, int M, long long sb,
+                                          long long sc, long long sp, float alpha, float gamma, float fg_weight, float bg_weight,
+                                          float depth_min, float depth_max, void *stream);
+int mono_ddn_loss_weighted_ignore_bwd_f32(const float *logits, const float *boxes, const float *depth, const unsigned char *valid,
+                                          const float *box_weight, const float *ign_boxes, const unsigned char *ign_valid,
+                                          const float *grad_total, float *grad_logits, int B, int C, int H, int W, int N, int M,
+                                          long long sb, long long sc, long long sp, float alpha, float gamma, float fg_weight,
+                                          float bg_weight, float depth_min, float depth_max, void *stream);
 
 /* Expected depth of the bin distribution (depth_predictor/depth_predictor.py:90-91): out [B, H, W] = sum_c softmax(logits)_c *
  * values[c]; logits [B, C, H, W] with (batch, channel, pixel) strides as above.  backward: grad_logits (same strides) =

@@ -21,13 +21,26 @@ struct DdnParams {
   float alpha, gamma, fg_weight, bg_weight, depth_min, depth_max, eps;
 };
 
+// Ignore regions of the IG instantiations: boxes [B, M, 4] = xyxy in depth-map pixels (float), valid [B, M] (bytes), count
+// [blocks] = ignored live pixels of each block (forward only).  All null and never read without IG.
+struct DdnIgnore {
+  const float *boxes;
+  const unsigned char *valid;
+  int *count;
+  int M;
+};
+
 // target bin and weight of pixel (b, y, x): boxes [B, N, 4] = xyxy in depth-map pixels (float), depth [B, N], valid [B, N].
 // BW: per-box weights bw [B, N] (nullptr and never read without BW); a foreground pixel weighs fg_weight * bw of the LOWEST slot among
 // the covering boxes of the nearest depth (slot order, strict <).  A box of weight 0 paints its depth like any other.
-template <bool BW>
+// IG: ``ignored`` = the pixel is NOT foreground and some valid ignore box g has x >= floorf(g.x1), x < ceilf(g.x2), y >= floorf(g.y1),
+// y < ceilf(g.y2) -- compared in float32 on the floats themselves (a NaN coordinate covers nothing, no float is converted to an
+// integer), rounded outward like a target box but WITHOUT the slice wrap of a negative start: x1 = -3.5 covers from column 0.
+// Foreground wins: a pixel under a target box keeps its term and its weight (fg_weight * 0 of a label of weight 0 included).
+template <bool BW, bool IG = false>
 __device__ __forceinline__ void ddn_target(const DdnParams &p, const float *__restrict__ boxes, const float *__restrict__ depth,
                                            const unsigned char *__restrict__ valid, const float *__restrict__ bw, int b, int y, int x,
-                                           int &bin, float &weight) {
+                                           int &bin, float &weight, const DdnIgnore &ig = DdnIgnore(), bool *ignored = nullptr) {
   float nearest = INFINITY, wbox = 1.f;
   bool fg = false;
   for (int i = 0; i < p.N; ++i) {
@@ -55,6 +68,16 @@ __device__ __forceinline__ void ddn_target(const DdnParams &p, const float *__re
   bin = bad ? num_bins : (int)idx;
   if constexpr (BW) weight = fg ? p.fg_weight * wbox : p.bg_weight;
   else weight = fg ? p.fg_weight : p.bg_weight;
+  if constexpr (IG) {
+    bool hit = false;
+    const float fx = (float)x, fy = (float)y;
+    for (int g = 0; g < ig.M; ++g) {
+      if (!ig.valid[b * ig.M + g]) continue;
+      const float *gx = ig.boxes + ((long long)b * ig.M + g) * 4;
+      hit = hit || (fx >= floorf(gx[0]) && fx < ceilf(gx[2]) && fy >= floorf(gx[1]) && fy < ceilf(gx[3]));
+    }
+    *ignored = hit && !fg;
+  }
 }
 
 constexpr int kDdnLanes = 8;          // lanes of one pixel: lane j takes bins j, j + 8, ... (an aligned group of 8 lanes of a wave)
@@ -66,10 +89,14 @@ __device__ __forceinline__ float group8_sum(float v) {
 }
 
 // partial[block] = sum over the block's pixels of weight * pixel loss   (the host sums the partials and divides)
-template <bool BW>
+// IG: an ignored pixel contributes none of its C terms -- its logits are not read (0 stands in, so that its eight lanes run every
+// shuffle like the others) and its sum is selected away, not multiplied by 0; ig.count[block] = ignored live pixels of the block,
+// counted by lane 0 of each pixel and reduced like the loss.  The divisor stays B H W.
+template <bool BW, bool IG = false>
 __global__ __launch_bounds__(256) void ddn_loss_fwd_kernel(const float *__restrict__ logits, const float *__restrict__ boxes,
                                                            const float *__restrict__ depth, const unsigned char *__restrict__ valid,
-                                                           const float *__restrict__ bw, float *__restrict__ partial, const DdnParams p) {
+                                                           const float *__restrict__ bw, float *__restrict__ partial, const DdnParams p,
+                                                           const DdnIgnore ig = DdnIgnore()) {
   __shared__ float red[4];
   const int slot = blockIdx.x * 256 + threadIdx.x, n_pix = p.B * p.H * p.W;
   const int sub = slot & (kDdnLanes - 1);
@@ -77,24 +104,37 @@ __global__ __launch_bounds__(256) void ddn_loss_fwd_kernel(const float *__restri
   const int pix = live ? slot / kDdnLanes : n_pix - 1;                 // (dead lanes shadow the last pixel: the shuffles stay uniform)
   const int b = pix / (p.H * p.W), hw = pix - b * p.H * p.W, y = hw / p.W, x = hw - y * p.W;
   int bin; float weight;
-  ddn_target<BW>(p, boxes, depth, valid, bw, b, y, x, bin, weight);
+  bool ign = false;
+  if constexpr (IG) ddn_target<BW, true>(p, boxes, depth, valid, bw, b, y, x, bin, weight, ig, &ign);
+  else ddn_target<BW>(p, boxes, depth, valid, bw, b, y, x, bin, weight);
   const float *z = logits + b * p.sb + hw * p.sp;
+  auto zc = [&](int c) { if constexpr (IG) return ign ? 0.f : z[c * p.sc]; else return z[c * p.sc]; };
   float mx = -INFINITY;
-  for (int c = sub; c < p.C; c += kDdnLanes) mx = fmaxf(mx, z[c * p.sc]);
+  for (int c = sub; c < p.C; c += kDdnLanes) mx = fmaxf(mx, zc(c));
   mx = group8_max(mx);
   float sum = 0.f;
-  for (int c = sub; c < p.C; c += kDdnLanes) sum += expf(z[c * p.sc] - mx);
+  for (int c = sub; c < p.C; c += kDdnLanes) sum += expf(zc(c) - mx);
   const float lse = mx + logf(group8_sum(sum));
   float loss = 0.f;
   for (int c = sub; c < p.C; c += kDdnLanes) {
-    const float ls = z[c * p.sc] - lse, pc = expf(ls);
+    const float ls = zc(c) - lse, pc = expf(ls);
     const float focal = -p.alpha * powf(1.f - pc, p.gamma) * ls;
     loss += ((c == bin ? 1.f : 0.f) + p.eps) * focal;
   }
   loss = live ? loss * weight : 0.f;
+  if constexpr (IG) loss = ign ? 0.f : loss;
   for (int o = 32; o > 0; o >>= 1) loss += __shfl_xor(loss, o);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = loss;
-  __syncthreads();
+  if constexpr (IG) {
+    __shared__ int redc[4];
+    int cnt = (live && ign && sub == 0) ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if ((threadIdx.x & 63) == 0) redc[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) ig.count[blockIdx.x] = redc[0] + redc[1] + redc[2] + redc[3];
+  } else {
+    __syncthreads();
+  }
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
@@ -107,39 +147,46 @@ __device__ __forceinline__ float focal_dp_times_p(const DdnParams &p, float ls, 
 }
 
 // grad_logits = g_scale * weight * d(pixel loss) / d logits, g_scale = grad of the total / number of pixels (device scalar)
-template <bool BW>
+// IG: the C gradients of an ignored pixel are written as +0.0 (grad_logits is uninitialised memory), its logits are not read; the
+// only early return is the dead lanes', behind the last shuffle.
+template <bool BW, bool IG = false>
 __global__ __launch_bounds__(256) void ddn_loss_bwd_kernel(const float *__restrict__ logits, const float *__restrict__ boxes,
                                                            const float *__restrict__ depth, const unsigned char *__restrict__ valid,
                                                            const float *__restrict__ bw, const float *__restrict__ grad_total,
-                                                           float *__restrict__ grad_logits, const DdnParams p) {
+                                                           float *__restrict__ grad_logits, const DdnParams p,
+                                                           const DdnIgnore ig = DdnIgnore()) {
   const int slot = blockIdx.x * 256 + threadIdx.x, n_pix = p.B * p.H * p.W;
   const int sub = slot & (kDdnLanes - 1);
   const bool live = slot / kDdnLanes < n_pix;
   const int pix = live ? slot / kDdnLanes : n_pix - 1;
   const int b = pix / (p.H * p.W), hw = pix - b * p.H * p.W, y = hw / p.W, x = hw - y * p.W;
   int bin; float weight;
-  ddn_target<BW>(p, boxes, depth, valid, bw, b, y, x, bin, weight);
+  bool ign = false;
+  if constexpr (IG) ddn_target<BW, true>(p, boxes, depth, valid, bw, b, y, x, bin, weight, ig, &ign);
+  else ddn_target<BW>(p, boxes, depth, valid, bw, b, y, x, bin, weight);
   const float *z = logits + b * p.sb + hw * p.sp;
   float *gz = grad_logits + b * p.sb + hw * p.sp;
+  auto zc = [&](int c) { if constexpr (IG) return ign ? 0.f : z[c * p.sc]; else return z[c * p.sc]; };
   float mx = -INFINITY;
-  for (int c = sub; c < p.C; c += kDdnLanes) mx = fmaxf(mx, z[c * p.sc]);
+  for (int c = sub; c < p.C; c += kDdnLanes) mx = fmaxf(mx, zc(c));
   mx = group8_max(mx);
   float sum = 0.f;
-  for (int c = sub; c < p.C; c += kDdnLanes) sum += expf(z[c * p.sc] - mx);
+  for (int c = sub; c < p.C; c += kDdnLanes) sum += expf(zc(c) - mx);
   const float lse = mx + logf(group8_sum(sum));
   // L = sum_c a_c f(p_c), f = -alpha (1 - p)^gamma log p;  dL/dz_k = t_k - p_k sum_c t_c  with  t_c = a_c f'(p_c) p_c
   float T = 0.f;
   for (int c = sub; c < p.C; c += kDdnLanes) {
-    const float ls = z[c * p.sc] - lse, pc = expf(ls), om = 1.f - pc;
+    const float ls = zc(c) - lse, pc = expf(ls), om = 1.f - pc;
     T += ((c == bin ? 1.f : 0.f) + p.eps) * focal_dp_times_p(p, ls, pc, om);
   }
   T = group8_sum(T);
   if (!live) return;
   const float scale = grad_total[0] * weight / (float)n_pix;
   for (int c = sub; c < p.C; c += kDdnLanes) {
-    const float ls = z[c * p.sc] - lse, pc = expf(ls), om = 1.f - pc;
+    const float ls = zc(c) - lse, pc = expf(ls), om = 1.f - pc;
     const float t = ((c == bin ? 1.f : 0.f) + p.eps) * focal_dp_times_p(p, ls, pc, om);
-    gz[c * p.sc] = scale * (t - pc * T);
+    if constexpr (IG) gz[c * p.sc] = ign ? 0.f : scale * (t - pc * T);
+    else gz[c * p.sc] = scale * (t - pc * T);
   }
 }
 

@@ -1494,6 +1494,65 @@ int mono_ddn_loss_weighted_bwd_f32(const float *logits, const float *boxes, cons
   return (int)hipGetLastError();
 }
 
+// The four above with ignore regions: ign_boxes [B, M, 4] xyxy in depth-map pixels (float32), ign_valid [B, M] (bytes).  A pixel that
+// no valid target box covers and some valid ignore box does (float32 comparisons against floorf / ceilf of the corners, no slice wrap)
+// contributes none of its C terms; its gradients are +0.0.  ign_count [mono_ddn_loss_blocks] = ignored live pixels of each block.
+static mono::DdnIgnore ddn_ignore(const float *ign_boxes, const unsigned char *ign_valid, int *ign_count, int M) {
+  mono::DdnIgnore ig;
+  ig.boxes = ign_boxes; ig.valid = ign_valid; ig.count = ign_count; ig.M = M;
+  return ig;
+}
+
+int mono_ddn_loss_ignore_fwd_f32(const float *logits, const float *boxes, const float *depth, const unsigned char *valid,
+                                 const float *ign_boxes, const unsigned char *ign_valid, float *partial, int *ign_count, int B, int C,
+                                 int H, int W, int N, int M, long long sb, long long sc, long long sp, float alpha, float gamma,
+                                 float fg_weight, float bg_weight, float depth_min, float depth_max, void *stream) {
+  if (!logits || !boxes || !depth || !valid || !ign_boxes || !ign_valid || !partial || !ign_count) return -1;
+  if (B <= 0 || C <= 1 || H <= 0 || W <= 0 || N <= 0 || M <= 0) return -2;
+  const mono::DdnParams p = ddn_params(B, C, H, W, N, sb, sc, sp, alpha, gamma, fg_weight, bg_weight, depth_min, depth_max);
+  mono::ddn_loss_fwd_kernel<false, true><<<mono_ddn_loss_blocks(B, H, W), 256, 0, (hipStream_t)stream>>>(
+      logits, boxes, depth, valid, nullptr, partial, p, ddn_ignore(ign_boxes, ign_valid, ign_count, M));
+  return (int)hipGetLastError();
+}
+
+int mono_ddn_loss_weighted_ignore_fwd_f32(const float *logits, const float *boxes, const float *depth, const unsigned char *valid,
+                                          const float *box_weight, const float *ign_boxes, const unsigned char *ign_valid,
+                                          float *partial, int *ign_count, int B, int C, int H, int W, int N, int M, long long sb,
+                                          long long sc, long long sp, float alpha, float gamma, float fg_weight, float bg_weight,
+                                          float depth_min, float depth_max, void *stream) {
+  if (!logits || !boxes || !depth || !valid || !box_weight || !ign_boxes || !ign_valid || !partial || !ign_count) return -1;
+  if (B <= 0 || C <= 1 || H <= 0 || W <= 0 || N <= 0 || M <= 0) return -2;
+  const mono::DdnParams p = ddn_params(B, C, H, W, N, sb, sc, sp, alpha, gamma, fg_weight, bg_weight, depth_min, depth_max);
+  mono::ddn_loss_fwd_kernel<true, true><<<mono_ddn_loss_blocks(B, H, W), 256, 0, (hipStream_t)stream>>>(
+      logits, boxes, depth, valid, box_weight, partial, p, ddn_ignore(ign_boxes, ign_valid, ign_count, M));
+  return (int)hipGetLastError();
+}
+
+int mono_ddn_loss_ignore_bwd_f32(const float *logits, const float *boxes, const float *depth, const unsigned char *valid,
+                                 const float *ign_boxes, const unsigned char *ign_valid, const float *grad_total, float *grad_logits,
+                                 int B, int C, int H, int W, int N, int M, long long sb, long long sc, long long sp, float alpha,
+                                 float gamma, float fg_weight, float bg_weight, float depth_min, float depth_max, void *stream) {
+  if (!logits || !boxes || !depth || !valid || !ign_boxes || !ign_valid || !grad_total || !grad_logits) return -1;
+  if (B <= 0 || C <= 1 || H <= 0 || W <= 0 || N <= 0 || M <= 0) return -2;
+  const mono::DdnParams p = ddn_params(B, C, H, W, N, sb, sc, sp, alpha, gamma, fg_weight, bg_weight, depth_min, depth_max);
+  mono::ddn_loss_bwd_kernel<false, true><<<mono_ddn_loss_blocks(B, H, W), 256, 0, (hipStream_t)stream>>>(
+      logits, boxes, depth, valid, nullptr, grad_total, grad_logits, p, ddn_ignore(ign_boxes, ign_valid, nullptr, M));
+  return (int)hipGetLastError();
+}
+
+int mono_ddn_loss_weighted_ignore_bwd_f32(const float *logits, const float *boxes, const float *depth, const unsigned char *valid,
+                                          const float *box_weight, const float *ign_boxes, const unsigned char *ign_valid,
+                                          const float *grad_total, float *grad_logits, int B, int C, int H, int W, int N, int M,
+                                          long long sb, long long sc, long long sp, float alpha, float gamma, float fg_weight,
+                                          float bg_weight, float depth_min, float depth_max, void *stream) {
+  if (!logits || !boxes || !depth || !valid || !box_weight || !ign_boxes || !ign_valid || !grad_total || !grad_logits) return -1;
+  if (B <= 0 || C <= 1 || H <= 0 || W <= 0 || N <= 0 || M <= 0) return -2;
+  const mono::DdnParams p = ddn_params(B, C, H, W, N, sb, sc, sp, alpha, gamma, fg_weight, bg_weight, depth_min, depth_max);
+  mono::ddn_loss_bwd_kernel<true, true><<<mono_ddn_loss_blocks(B, H, W), 256, 0, (hipStream_t)stream>>>(
+      logits, boxes, depth, valid, box_weight, grad_total, grad_logits, p, ddn_ignore(ign_boxes, ign_valid, nullptr, M));
+  return (int)hipGetLastError();
+}
+
 
 // ---- expected depth over the bin distribution (ddn_loss.hip) -------------------------------------------------------------
 int mono_depth_expect_fwd_f32(const float *logits, const float *values, float *out, int B, int C, int H, int W, long long sb,

@@ -89,6 +89,9 @@ class Detector:
         self.topk = cfg["tester"]["topk"]
         # tester.nms_iou / flip_tta / fuse: duplicate suppression and flip-view fusion of the rows (monosowa_amd/fuse.py); None: off
         self.fuse = fuse_config(cfg["tester"])
+        # tester.dontcare_below: rows scoring below it are written by write_kitti as DontCare lines; None: off
+        from .helpers.tester_helper import check_dontcare_below
+        self.dontcare_below = check_dontcare_below(cfg["tester"].get("dontcare_below"), self.threshold)
         self.engine = InferenceEngine(self.model, self.device, topk=self.topk, max_objs=self.dataset.max_objs,
                                       decode=(self.dataset.cls_mean_size, self.threshold), fuse=self.fuse)
 
@@ -160,7 +163,7 @@ class Detector:
     def write_kitti(self, rows, ids, directory):
         """One KITTI result file per frame, ``%06d.txt`` of its id: the files ``Tester.save_results`` writes for these rows."""
         from .helpers.tester_helper import write_kitti_results
-        write_kitti_results(dict(zip(ids, rows)), self.class_name, os.fspath(directory))
+        write_kitti_results(dict(zip(ids, rows)), self.class_name, os.fspath(directory), dontcare_below=self.dontcare_below)
 
     def close(self):
         self.engine.close()

@@ -65,6 +65,8 @@ class Tester(object):
         # tester.nms_iou / flip_tta / fuse: duplicate suppression and flip-view fusion on the device (monosowa_amd/fuse.py); None: off
         from ..fuse import fuse_config
         self.fuse = fuse_config(cfg)
+        # tester.dontcare_below: rows scoring below it are written as DontCare lines (ignore regions of the next round); None: off
+        self.dontcare_below = check_dontcare_below(cfg.get("dontcare_below"), cfg.get("threshold", 0.2))
 
     def test(self):
         assert self.cfg["mode"] in ["single", "all"]
@@ -149,7 +151,7 @@ class Tester(object):
         return results
 
     def save_results(self, results):
-        write_kitti_results(results, self.class_name, os.path.join(self.output_dir, "outputs", "data"))
+        write_kitti_results(results, self.class_name, os.path.join(self.output_dir, "outputs", "data"), dontcare_below=self.dontcare_below)
 
     def evaluate(self):
         results_dir = os.path.join(self.output_dir, "outputs", "data")
@@ -164,12 +166,27 @@ class Tester(object):
         return 0.0
 
 
-def write_kitti_results(results, class_name, output_dir):
-    """One KITTI label file per image: 'Class 0.0 0 alpha x1 y1 x2 y2 h w l x y z ry score', '%.2f'."""
+def check_dontcare_below(value, threshold):
+    """``tester.dontcare_below``: a float in (tester.threshold, 1]; absent or None: off (None)."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (float(threshold) < float(value) <= 1.0):
+        raise ValueError("tester.dontcare_below = %r is not a number in (tester.threshold = %r, 1]" % (value, threshold))
+    return float(value)
+
+
+def write_kitti_results(results, class_name, output_dir, dontcare_below=None):
+    """One KITTI label file per image: 'Class 0.0 0 alpha x1 y1 x2 y2 h w l x y z ry score', '%.2f'.
+    ``dontcare_below`` X: a row with score < X is written, in its place, as 'DontCare -1 -1 -10.00 x1 y1 x2 y2 -1.00 -1.00 -1.00
+    -1000.00 -1000.00 -1000.00 -10.00 score' -- the same 16 columns, the box and the score as '%.2f'; a NaN score is not below X."""
     os.makedirs(output_dir, exist_ok=True)
     for img_id, preds in results.items():
         with open(os.path.join(output_dir, "{:06d}.txt".format(int(img_id))), "w") as f:
             for p in preds:
+                if dontcare_below is not None and p[-1] < dontcare_below:
+                    f.write("DontCare -1 -1 -10.00 {:.2f} {:.2f} {:.2f} {:.2f} -1.00 -1.00 -1.00 -1000.00 -1000.00 -1000.00 -10.00 {:.2f}\n".format(
+                        p[2], p[3], p[4], p[5], p[-1]))
+                    continue
                 f.write("{} 0.0 0".format(class_name[int(p[0])]))
                 for j in range(1, len(p)):
                     f.write(" {:.2f}".format(p[j]))

@@ -525,8 +525,13 @@ class Trainer(object):
         if report is not None:
             print("grad_norm: %.4g, skipped: %d\n" % (report["grad_norm"], report["skipped_total"]))
         ignore = self.detr_loss.ignore_report() if hasattr(self.detr_loss, "ignore_report") else None
+        # model.ignore_depth_map: depth-map pixels left out of loss_depth_map in this step (None with the key off)
+        px = self.detr_loss.ignore_depth_report() if hasattr(self.detr_loss, "ignore_depth_report") else None
+        px_text = "" if px is None else "ignored px: %d of %d" % px
         if ignore is not None:                             # dataset.ignore_regions: queries left out of loss_ce in this step, all layers
-            print("ignored: %d of %d\n" % (sum(ignore[0]), len(ignore[0]) * ignore[1]))
+            print("ignored: %d of %d%s\n" % (sum(ignore[0]), len(ignore[0]) * ignore[1], ", " + px_text if px_text else ""))
+        elif px_text:
+            print(px_text + "\n")
 
     @staticmethod
     def prepare_targets(targets, batch_size):

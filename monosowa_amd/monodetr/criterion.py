@@ -82,6 +82,15 @@ def check_ignore_ioa(value):
     return float(value)
 
 
+def check_ignore_depth_map(value):
+    """``model.ignore_depth_map``: a bool; absent, None or False: off."""
+    if value is None:
+        return False
+    if not isinstance(value, bool):
+        raise ValueError("model.ignore_depth_map = %r is not a bool" % (value,))
+    return value
+
+
 FUSED_FOCAL = True       # classification side (focal sums, class / cardinality errors) as one HIP kernel each way
 FUSED_MATCHED = True     # matched-pair losses through the HIP kernels on the GPU (False: the PyTorch formulation below)
 
@@ -191,6 +200,7 @@ class SetCriterion(nn.Module):
     # known (``observe``: one launch, nothing waits); None: nothing is launched, allocated or read for it
     audit = None
     _ignore_last = None      # what ignore_report reads: the flags, their per-layer counts and the pairs of the last forward with ignore boxes
+    _ignore_depth_last = None      # what ignore_depth_report reads: (ignored-pixel counts, B * H * W) of the last forward that ignored pixels
 
     def __init__(self, num_classes, matcher, weight_dict, focal_alpha, losses, group_num=11, cfg=None,
                  depth_map_size=(80, 24), fast=True):
@@ -213,6 +223,8 @@ class SetCriterion(nn.Module):
         # share of a query box's own area inside an ignore box from which an unmatched query is left out of loss_ce; read only when the
         # targets carry ignore boxes (dataset.ignore_regions)
         self.ignore_ioa = check_ignore_ioa(cfg.get("ignore_ioa", 0.5) if cfg is not None else 0.5)
+        # depth-map pixels under an ignore box (and under no target box) leave loss_depth_map; acts only on targets with ignore boxes
+        self.ignore_depth_map = check_ignore_depth_map(cfg.get("ignore_depth_map") if cfg is not None else None)
         if self.use_tfl or self.use_mask_loss:
             raise NotImplementedError("use_tfl / use_mask_loss need pytorch3d + open3d rendering that the reference "
                                       "itself does not import; they are off in every shipped config")
@@ -348,10 +360,26 @@ class SetCriterion(nn.Module):
         scale = torch.tensor([w, h, w, h], device=logits.device, dtype=logits.dtype)
         boxes = box_ops.box_cxcywh_to_xyxy(torch.cat([t["boxes"] for t in targets], dim=0) * scale)
         centre_depth = torch.cat([t["depth"] for t in targets], dim=0).squeeze(dim=1)
+        ignore = self._ignore_depth_pair(targets, logits.device)
+        if ignore is not None:
+            box_weight = torch.cat([t["label_weight"] for t in targets], dim=0) if _has_label_weight(targets) else None
+            loss = self.ddn_loss(logits, boxes, num_gt_per_img, centre_depth, box_weight=box_weight, ignore=ignore)
+            self._ignore_depth_last = (self.ddn_loss.ign_count, logits.shape[0] * logits.shape[2] * logits.shape[3])
+            return {"loss_depth_map": loss}
         if _has_label_weight(targets):
             return {"loss_depth_map": self.ddn_loss(logits, boxes, num_gt_per_img, centre_depth,
                                                     box_weight=torch.cat([t["label_weight"] for t in targets], dim=0))}
         return {"loss_depth_map": self.ddn_loss(logits, boxes, num_gt_per_img, centre_depth)}
+
+    def _ignore_depth_pair(self, targets, device):
+        """(ignore boxes [B, M, 4] in depth-map pixels -- the normalised boxes times (w, h, w, h) in float32, one rounding per coordinate,
+        the multiply the target boxes get --, mask [B, M] bool) for the depth-map loss; None with model.ignore_depth_map off or on a
+        batch without ignore boxes."""
+        regions = _ignore_regions(targets)
+        if not self.ignore_depth_map or regions is None:
+            return None
+        w, h = self.depth_map_size
+        return regions[0].to(torch.float32) * _dev([w, h, w, h], torch.float32, device), regions[1].to(torch.bool)
 
     def loss_tfl(self, outputs, targets, indices, num_boxes, info=None):
         dev = outputs["pred_logits"].device
@@ -370,6 +398,7 @@ class SetCriterion(nn.Module):
         job-wide -- nothing is all-reduced then.  The Trainer's gradient accumulation passes the cycle-wide count."""
         if _ignore_regions(targets) is None:
             self._ignore_last = None
+        self._ignore_depth_last = None
         if self.fast:
             return self.forward_fast(outputs, targets, num_boxes)
         return self.forward_layerwise(outputs, targets, mask_dict, info, num_boxes)
@@ -433,13 +462,21 @@ class SetCriterion(nn.Module):
             valid_t = torch.zeros((B, 1), dtype=torch.bool, device=dev)
             boxes2d = torch.zeros((B, 1, 4), device=dev, dtype=logits.dtype)
             depth2d = torch.zeros((B, 1), device=dev, dtype=logits.dtype)
-        if weighted:
+        regions = _ignore_regions(targets)
+        ignore_px = self._ignore_depth_pair(targets, dev)
+        if ignore_px is not None:                   # model.ignore_depth_map: the ignore-region kernels, the same place in the queue
+            map_logits = outputs["pred_depth_map_logits"]
+            weight2d = None
+            if weighted:
+                weight2d = t_weight.to(logits.dtype)[slot_t] if maxn else torch.ones((B, 1), device=dev, dtype=logits.dtype)
+            loss_depth_map = self.ddn_loss.forward_padded(map_logits, boxes2d, depth2d, valid_t, box_weight=weight2d, ignore=ignore_px)
+            self._ignore_depth_last = (self.ddn_loss.ign_count, map_logits.shape[0] * map_logits.shape[2] * map_logits.shape[3])
+        elif weighted:
             weight2d = t_weight.to(logits.dtype)[slot_t] if maxn else torch.ones((B, 1), device=dev, dtype=logits.dtype)
             loss_depth_map = self.ddn_loss.forward_padded(outputs["pred_depth_map_logits"], boxes2d, depth2d, valid_t, box_weight=weight2d)
         else:
             loss_depth_map = self.ddn_loss.forward_padded(outputs["pred_depth_map_logits"], boxes2d, depth2d, valid_t)
         # ignore regions: which queries sit on an ignore box does not depend on the matching either -- one launch, here
-        regions = _ignore_regions(targets)
         flags = None
         if regions is not None:
             flags, flag_counts = ignore_flags(boxes.detach(), regions[0], regions[1], self.ignore_ioa)
@@ -593,6 +630,15 @@ class SetCriterion(nn.Module):
         matched = flags[torch.arange(NL, device=flags.device).view(NL, 1).expand(NL, K), idx[0], idx[1]].sum(1, dtype=torch.int64)
         ignored = (counts.to(torch.int64) - matched).tolist()
         return [int(v) for v in ignored], int(flags[0].numel())
+
+    def ignore_depth_report(self):
+        """(ignored_pixels, B * H * W) of the last forward that left depth-map pixels out of loss_depth_map (model.ignore_depth_map on a
+        batch with ignore boxes): the pixels under a valid ignore box and under no target box.  Reads the device (a synchronisation)
+        like ``ignore_report``; None before any such forward, and after a forward without regions or with the key off."""
+        rec = self._ignore_depth_last
+        if rec is None or rec[0] is None:
+            return None
+        return int(rec[0].sum()), int(rec[1])
 
     @staticmethod
     def _finish(per_layer, NL, dev, loss_depth_map, mat=None):

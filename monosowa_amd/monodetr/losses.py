@@ -108,19 +108,35 @@ class DDNLoss(nn.Module):
             start += n
         return canvas
 
-    def forward_padded(self, depth_logits, boxes_padded, depth_padded, valid, box_weight=None):
+    ign_count = None      # ignored pixels of the last forward with ``ignore`` (an int tensor, any shape: its sum counts), else None
+
+    def _leave_out(self, depth_logits, ignore, fg):
+        """The plain formulation's ignore regions: (logits with the ignored pixels' C values replaced by a constant -- their gradient is
+        then exactly zero and a non-finite value there reaches nothing --, the ignored mask [B, H, W])."""
+        ign = rasterize_ignore(ignore[0], ignore[1], fg, depth_logits.shape[2], depth_logits.shape[3])
+        self.ign_count = ign.sum()
+        return torch.where(ign.unsqueeze(1), depth_logits.new_zeros(()), depth_logits), ign
+
+    def forward_padded(self, depth_logits, boxes_padded, depth_padded, valid, box_weight=None, ignore=None):
         """Same loss from padded per-image targets ([B,N,4] xyxy in depth-map pixels, [B,N], [B,N] bool) with no
         host round trip.  Equal depths aside (where the painted value is the same anyway) it reproduces
         ``forward`` exactly; downsample_factor must be 1 (the only value the reference uses).
         ``box_weight`` [B,N]: per-box weights -- a foreground pixel weighs fg_weight times the weight of the lowest slot among its
-        covering boxes of the nearest depth (``rasterize_box_weights``); the painted depth, the background and the divisor stay."""
+        covering boxes of the nearest depth (``rasterize_box_weights``); the painted depth, the background and the divisor stay.
+        ``ignore`` = (boxes_px [B,M,4] xyxy in depth-map pixels, mask [B,M] bool): a pixel that is not foreground and lies under a
+        valid ignore box (``rasterize_ignore``) contributes none of its terms and gets no gradient; the divisor stays."""
         assert self.downsample_factor == 1
         B, _, H, W = depth_logits.shape
+        self.ign_count = None
         if FUSED_DDN:
             from ..pointwise import ddn_loss, ddn_loss_supported
-            if ddn_loss_supported(depth_logits, boxes_padded, depth_padded, valid) and \
+            if ddn_loss_supported(depth_logits, boxes_padded, depth_padded, valid, ignore) and \
                     (box_weight is None or box_weight.dtype == torch.float32):
                 # rasterisation, LID binning, softmax focal loss and balancing: one HIP kernel each way (csrc/ddn_loss.hip)
+                if ignore is not None:
+                    loss, self.ign_count = ddn_loss(depth_logits, boxes_padded, depth_padded, valid, self.alpha, self.gamma, self.fg_weight,
+                                                    self.bg_weight, weight=box_weight, ignore=ignore, return_count=True)
+                    return loss
                 if box_weight is not None:
                     return ddn_loss(depth_logits, boxes_padded, depth_padded, valid, self.alpha, self.gamma, self.fg_weight, self.bg_weight,
                                     weight=box_weight)
@@ -130,19 +146,37 @@ class DDNLoss(nn.Module):
         b[..., 2:] = torch.ceil(b[..., 2:])
         depth_maps, fg = rasterize_boxes(b.long(), depth_padded, valid, H, W)
         target = lid_bin_indices(depth_maps, target=True)
+        if ignore is not None:
+            depth_logits, ign = self._leave_out(depth_logits, ignore, fg)
         loss = softmax_focal_loss(depth_logits, target, self.alpha, self.gamma)
         if box_weight is not None:
             wmap = rasterize_box_weights(b.long(), depth_padded, valid, box_weight.to(loss.dtype), H, W)
-            loss = loss * (self.fg_weight * fg * wmap + self.bg_weight * (~fg))
+            factor = self.fg_weight * fg * wmap + self.bg_weight * (~fg)
         else:
-            loss = loss * (self.fg_weight * fg + self.bg_weight * (~fg))
+            factor = self.fg_weight * fg + self.bg_weight * (~fg)
+        if ignore is not None:
+            factor = torch.where(ign, factor.new_zeros(()), factor)
+        loss = loss * factor
         return (loss * fg).sum() / fg.numel() + (loss * (~fg)).sum() / fg.numel()
 
-    def forward(self, depth_logits, gt_boxes2d, num_gt_per_img, gt_center_depth, box_weight=None):
-        """``box_weight`` [sum(num_gt_per_img)]: per-box weights, see ``forward_padded``."""
+    def forward(self, depth_logits, gt_boxes2d, num_gt_per_img, gt_center_depth, box_weight=None, ignore=None):
+        """``box_weight`` [sum(num_gt_per_img)]: per-box weights, ``ignore``: ignore regions, see ``forward_padded``."""
+        self.ign_count = None
         if box_weight is not None:
-            return self._forward_weighted(depth_logits, gt_boxes2d, num_gt_per_img, gt_center_depth, box_weight)
+            return self._forward_weighted(depth_logits, gt_boxes2d, num_gt_per_img, gt_center_depth, box_weight, ignore)
         B, _, H, W = depth_logits.shape
+        if ignore is not None:
+            boxes_int = _int_boxes(gt_boxes2d)
+            depth_maps = self.paint_boxes((B, H, W), boxes_int, num_gt_per_img, gt_center_depth,
+                                          dtype=depth_logits.dtype, device=depth_logits.device)
+            target = lid_bin_indices(depth_maps, target=True)
+            boxes_fg = _int_boxes(boxes_int.to(gt_boxes2d.dtype) / self.downsample_factor)
+            fg = self.paint_boxes((B, H, W), boxes_fg, num_gt_per_img, None, dtype=torch.bool, device=depth_logits.device)
+            depth_logits, ign = self._leave_out(depth_logits, ignore, fg)
+            loss = softmax_focal_loss(depth_logits, target, self.alpha, self.gamma)
+            weights = self.fg_weight * fg + self.bg_weight * (~fg)
+            loss = loss * torch.where(ign, weights.new_zeros(()), weights)
+            return (loss * fg).sum() / fg.numel() + (loss * (~fg)).sum() / fg.numel()
         boxes_int = _int_boxes(gt_boxes2d)
         depth_maps = self.paint_boxes((B, H, W), boxes_int, num_gt_per_img, gt_center_depth,
                                       dtype=depth_logits.dtype, device=depth_logits.device)
@@ -157,21 +191,25 @@ class DDNLoss(nn.Module):
         loss = loss * weights
         return (loss * fg).sum() / num_pixels + (loss * (~fg)).sum() / num_pixels
 
-    def _forward_weighted(self, depth_logits, gt_boxes2d, num_gt_per_img, gt_center_depth, box_weight):
+    def _forward_weighted(self, depth_logits, gt_boxes2d, num_gt_per_img, gt_center_depth, box_weight, ignore=None):
         """``DDNLoss.forward`` with per-box weights: the painted depth and the foreground mask are ``forward``'s; the weight of a
         foreground pixel follows the slot rule of ``rasterize_box_weights``."""
         B, _, H, W = depth_logits.shape
         boxes_int = _int_boxes(gt_boxes2d)
         depth_maps = self.paint_boxes((B, H, W), boxes_int, num_gt_per_img, gt_center_depth, dtype=depth_logits.dtype, device=depth_logits.device)
         target = lid_bin_indices(depth_maps, target=True)
-        loss = softmax_focal_loss(depth_logits, target, self.alpha, self.gamma)
         boxes_fg = _int_boxes(boxes_int.to(gt_boxes2d.dtype) / self.downsample_factor)
-        fg = self.paint_boxes((B, H, W), boxes_fg, num_gt_per_img, None, dtype=torch.bool, device=loss.device)
+        fg = self.paint_boxes((B, H, W), boxes_fg, num_gt_per_img, None, dtype=torch.bool, device=depth_logits.device)
+        if ignore is not None:
+            depth_logits, ign = self._leave_out(depth_logits, ignore, fg)
+        loss = softmax_focal_loss(depth_logits, target, self.alpha, self.gamma)
         pb, valid = _pad_per_image(boxes_fg, num_gt_per_img)
         pd, _ = _pad_per_image(gt_center_depth.reshape(-1), num_gt_per_img)
         pw, _ = _pad_per_image(box_weight.reshape(-1).to(loss.dtype), num_gt_per_img)
         wmap = rasterize_box_weights(pb, pd, valid, pw, H, W)
         weights = self.fg_weight * fg * wmap + self.bg_weight * (~fg)
+        if ignore is not None:
+            weights = torch.where(ign, weights.new_zeros(()), weights)
         num_pixels = fg.numel()
         loss = loss * weights
         return (loss * fg).sum() / num_pixels + (loss * (~fg)).sum() / num_pixels
@@ -191,6 +229,20 @@ def rasterize_box_weights(boxes_int, depths, valid, weights, H, W):
     first = (cover & (d == d.amin(dim=1, keepdim=True))).to(torch.uint8).argmax(dim=1)         # first maximum = lowest slot
     w = torch.gather(weights[..., None, None].expand(-1, -1, H, W), 1, first.unsqueeze(1)).squeeze(1)
     return torch.where(cover.any(dim=1), w, torch.ones((), dtype=weights.dtype, device=weights.device))
+
+
+def rasterize_ignore(boxes_px, mask, fg, H, W):
+    """[B,H,W] bool: the pixels that are NOT foreground (``fg`` [B,H,W] bool) and lie under a valid ignore box -- boxes_px [B,M,4] xyxy
+    in depth-map pixels, mask [B,M] bool; pixel (y, x) is under box g when x >= floor(g.x1), x < ceil(g.x2), y >= floor(g.y1) and
+    y < ceil(g.y2), compared on the floats themselves in the boxes' dtype (float32 in the criterion): a NaN coordinate covers nothing,
+    nothing is converted to an integer, and a negative start does not wrap as a target box's does (x1 = -3.5 covers from column 0)."""
+    x1, y1, x2, y2 = boxes_px.unbind(-1)
+    ys = torch.arange(H, device=boxes_px.device, dtype=boxes_px.dtype).view(1, 1, H, 1)
+    xs = torch.arange(W, device=boxes_px.device, dtype=boxes_px.dtype).view(1, 1, 1, W)
+    lo_x, hi_x = torch.floor(x1)[..., None, None], torch.ceil(x2)[..., None, None]
+    lo_y, hi_y = torch.floor(y1)[..., None, None], torch.ceil(y2)[..., None, None]
+    cover = (xs >= lo_x) & (xs < hi_x) & (ys >= lo_y) & (ys < hi_y) & mask[..., None, None]          # [B,M,H,W]
+    return cover.any(dim=1) & ~fg
 
 
 def _norm_slice(a, n):

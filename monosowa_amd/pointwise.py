@@ -19,7 +19,8 @@ SYMBOLS = ("mono_bias_act_f32", "mono_bias_relu_maxpool_nhwc_f32", "mono_conv1x1
            "mono_label_audit_f32", "mono_matched_losses_weighted_fwd_f32", "mono_matched_losses_weighted_bwd_f32", "mono_focal_weighted_fwd_f32",
            "mono_focal_weighted_bwd_f32", "mono_ddn_loss_weighted_fwd_f32", "mono_ddn_loss_weighted_bwd_f32", "mono_focal_weighted_max_cells",
            "mono_ignore_flags_f32", "mono_focal_ignore_fwd_f32", "mono_focal_ignore_bwd_f32", "mono_focal_weighted_ignore_fwd_f32",
-           "mono_focal_weighted_ignore_bwd_f32")
+           "mono_focal_weighted_ignore_bwd_f32", "mono_ddn_loss_ignore_fwd_f32", "mono_ddn_loss_ignore_bwd_f32",
+           "mono_ddn_loss_weighted_ignore_fwd_f32", "mono_ddn_loss_weighted_ignore_bwd_f32")
 _lib = None
 
 
@@ -164,6 +165,10 @@ def load():
         lib.mono_ddn_loss_weighted_fwd_f32.argtypes = [P] * 6 + [I] * 5 + [LL] * 3 + [F] * 6 + [P]
         lib.mono_ddn_loss_weighted_bwd_f32.restype = I
         lib.mono_ddn_loss_weighted_bwd_f32.argtypes = [P] * 7 + [I] * 5 + [LL] * 3 + [F] * 6 + [P]
+        for name, n_ptr in (("mono_ddn_loss_ignore_fwd_f32", 8), ("mono_ddn_loss_ignore_bwd_f32", 8), ("mono_ddn_loss_weighted_ignore_fwd_f32", 9),
+                            ("mono_ddn_loss_weighted_ignore_bwd_f32", 9)):
+            getattr(lib, name).restype = I
+            getattr(lib, name).argtypes = [P] * n_ptr + [I] * 6 + [LL] * 3 + [F] * 6 + [P]
         _lib = lib
     return _lib
 
@@ -1190,7 +1195,12 @@ def _ddn_strides(logits):
     return (sb, sc, sw) if sh == sw * logits.shape[3] else None
 
 
-def ddn_loss_supported(logits, boxes, depth, valid):
+def ddn_loss_supported(logits, boxes, depth, valid, ignore=None):
+    """``ignore`` = (boxes_px, mask) of the ignore-region kernels: float32 [B, M, 4] and bool [B, M], M >= 1, on the logits' device."""
+    if ignore is not None and not (ignore[0].dtype == torch.float32 and ignore[1].dtype == torch.bool and ignore[0].dim() == 3
+                                   and ignore[0].shape[1] >= 1 and ignore[0].device == logits.device
+                                   and ignore[1].device == logits.device):
+        return False
     return (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 4 and _ddn_strides(logits) is not None
             and boxes.dtype == torch.float32 and depth.dtype == torch.float32 and valid.dtype == torch.bool)
 
@@ -1297,8 +1307,95 @@ class _DDNLossWeighted(torch.autograd.Function):
         return (grad,) + (None,) * 10
 
 
-def ddn_loss(logits, boxes, depth, valid, alpha, gamma, fg_weight, bg_weight, depth_min=1e-3, depth_max=60.0, weight=None):
-    """``weight`` [B, N] float32: per-box weights (the weighted kernels); None: the unweighted launches."""
+def _ddn_ignore_call(which, weighted, logits, boxes, depth, valid, box_weight, ign_boxes, ign_valid, out_ptrs, consts):
+    """One launch of ``mono_ddn_loss[_weighted]_ignore_{fwd,bwd}_f32``: the sibling's arguments plus the ignore boxes, their mask and M."""
+    B, C, H, W = logits.shape
+    sb, sc, sp = _ddn_strides(logits)
+    name = "mono_ddn_loss_%signore_%s_f32" % ("weighted_" if weighted else "", which)
+    ptrs = [logits.data_ptr(), boxes.data_ptr(), depth.data_ptr(), valid.data_ptr()] + ([box_weight.data_ptr()] if weighted else []) \
+        + [ign_boxes.data_ptr(), ign_valid.data_ptr()] + list(out_ptrs)
+    code = getattr(load(), name)(*ptrs, B, C, H, W, boxes.shape[1], ign_boxes.shape[1], sb, sc, sp, *consts, raw_stream())
+    if code:
+        raise RuntimeError("%s failed with code %d" % (name, code))
+
+
+def _ddn_ignore_forward(ctx, weighted, logits, boxes, depth, valid, box_weight, ign_boxes, ign_valid, consts):
+    B, C, H, W = logits.shape
+    boxes, depth, valid = boxes.contiguous(), depth.contiguous(), valid.contiguous()
+    box_weight = box_weight.contiguous() if weighted else None
+    ign_boxes, ign_valid = ign_boxes.contiguous(), ign_valid.contiguous()
+    blocks = load().mono_ddn_loss_blocks(B, H, W)
+    partial = torch.empty(blocks, dtype=torch.float32, device=logits.device)
+    count = torch.empty(blocks, dtype=torch.int32, device=logits.device)
+    _ddn_ignore_call("fwd", weighted, logits, boxes, depth, valid, box_weight, ign_boxes, ign_valid,
+                     (partial.data_ptr(), count.data_ptr()), consts)
+    ctx.consts, ctx.weighted, ctx.eager = consts, weighted, None
+    if DDN_EAGER_BACKWARD and logits.requires_grad:          # as in _DDNLoss.forward: evaluated under the matcher's wait
+        one = torch.ones(1, dtype=torch.float32, device=logits.device)
+        grad = torch.empty_strided(logits.shape, logits.stride(), dtype=logits.dtype, device=logits.device)
+        _ddn_ignore_call("bwd", weighted, logits, boxes, depth, valid, box_weight, ign_boxes, ign_valid,
+                         (one.data_ptr(), grad.data_ptr()), consts)
+        ctx.save_for_backward(grad)
+        ctx.eager = True
+    else:
+        ctx.save_for_backward(*([logits, boxes, depth, valid] + ([box_weight] if weighted else []) + [ign_boxes, ign_valid]))
+    ctx.mark_non_differentiable(count)
+    return partial.sum() / (B * H * W), count
+
+
+def _ddn_ignore_backward(ctx, g, n_args):
+    if ctx.eager:
+        (grad,) = ctx.saved_tensors
+        return (grad * g,) + (None,) * (n_args - 1)
+    saved = ctx.saved_tensors
+    logits, boxes, depth, valid = saved[:4]
+    box_weight = saved[4] if ctx.weighted else None
+    ign_boxes, ign_valid = saved[-2:]
+    grad = torch.empty_strided(logits.shape, logits.stride(), dtype=logits.dtype, device=logits.device)
+    g = g.reshape(1).to(torch.float32).contiguous()
+    _ddn_ignore_call("bwd", ctx.weighted, logits, boxes, depth, valid, box_weight, ign_boxes, ign_valid, (g.data_ptr(), grad.data_ptr()),
+                     ctx.consts)
+    return (grad,) + (None,) * (n_args - 1)
+
+
+class _DDNLossIgnore(torch.autograd.Function):
+    """``_DDNLoss`` with ignore regions (``mono_ddn_loss_ignore_*``): ign_boxes [B, M, 4] xyxy in depth-map pixels, ign_valid [B, M]
+    bool.  Returns (loss, ign_count [blocks] int32: the ignored pixels of every block)."""
+    @staticmethod
+    def forward(ctx, logits, boxes, depth, valid, ign_boxes, ign_valid, alpha, gamma, fg_weight, bg_weight, depth_min, depth_max):
+        return _ddn_ignore_forward(ctx, False, logits, boxes, depth, valid, None, ign_boxes, ign_valid,
+                                   (alpha, gamma, fg_weight, bg_weight, depth_min, depth_max))
+
+    @staticmethod
+    def backward(ctx, g, _g_count):
+        return _ddn_ignore_backward(ctx, g, 12)
+
+
+class _DDNLossWeightedIgnore(torch.autograd.Function):
+    """``_DDNLossWeighted`` with ignore regions (``mono_ddn_loss_weighted_ignore_*``), as ``_DDNLossIgnore``."""
+    @staticmethod
+    def forward(ctx, logits, boxes, depth, valid, box_weight, ign_boxes, ign_valid, alpha, gamma, fg_weight, bg_weight, depth_min,
+                depth_max):
+        return _ddn_ignore_forward(ctx, True, logits, boxes, depth, valid, box_weight, ign_boxes, ign_valid,
+                                   (alpha, gamma, fg_weight, bg_weight, depth_min, depth_max))
+
+    @staticmethod
+    def backward(ctx, g, _g_count):
+        return _ddn_ignore_backward(ctx, g, 13)
+
+
+def ddn_loss(logits, boxes, depth, valid, alpha, gamma, fg_weight, bg_weight, depth_min=1e-3, depth_max=60.0, weight=None, ignore=None,
+             return_count=False):
+    """``weight`` [B, N] float32: per-box weights (the weighted kernels); None: the unweighted launches.
+    ``ignore`` = (boxes_px [B, M, 4] float32 xyxy in depth-map pixels, mask [B, M] bool): the ignore-region kernels; with
+    ``return_count`` the result is (loss, ign_count [blocks] int32)."""
+    if ignore is not None:
+        consts = (float(alpha), float(gamma), float(fg_weight), float(bg_weight), float(depth_min), float(depth_max))
+        if weight is not None:
+            loss, count = _DDNLossWeightedIgnore.apply(logits, boxes, depth, valid, weight.to(torch.float32), ignore[0], ignore[1], *consts)
+        else:
+            loss, count = _DDNLossIgnore.apply(logits, boxes, depth, valid, ignore[0], ignore[1], *consts)
+        return (loss, count) if return_count else loss
     if weight is not None:
         return _DDNLossWeighted.apply(logits, boxes, depth, valid, weight.to(torch.float32), float(alpha), float(gamma),
                                       float(fg_weight), float(bg_weight), float(depth_min), float(depth_max))
