@@ -4,6 +4,10 @@
  * Replaces lib/datasets/kitti/kitti_eval_python/rotate_iou.py:263-330 (`rotate_iou_gpu_eval`, a numba-CUDA kernel) and
  * the CPU loop of eval.py:197-230 (`d3_box_overlap`).  Device pointers, asynchronous on `stream`.
  * criterion: -1 IoU, 0 intersection / area of the first operand, 1 intersection / area of the second, 2 intersection.
+ * The intersection is the reference's quantity but not its method: the reference collects corners by >= tests on absolute
+ * coordinates and divides edge crossings by a determinant that vanishes for parallel edges, which scores identical boxes 0 or 1/3
+ * and collinear or one-ulp-apart boxes anything up to NaN.  Here one rectangle is clipped in the other's frame (float32), so that
+ * identical and edge-sharing boxes score their exact overlap, and a box with a side that is not > 0 intersects nothing.
  * Return value: 0, -1 (NULL pointer), -2 (bad size / criterion) or a hipError_t.
  */
 #ifndef MONOSOWA_KITTI_H

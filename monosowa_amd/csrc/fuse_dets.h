@@ -13,12 +13,13 @@
 //      the first seed in seed order -- or r becomes a seed.  n iterations of at most 4 ballots, wave-uniform control, bounded;
 //   6. a thread per cluster writes its row: the seed's row byte for byte (mode 0) or the score-weighted mean of its members summed
 //      in member (rank) order (mode 1); rows, support behind the clusters are zero.
-// Two candidates whose five float32 numbers are equal (finite, non-zero area) overlap by 1 without asking the routine: it collects
-// corners by >= tests that coincident edges pass or fail by rounding (tests/test_kitti_overlap.py notes the same of the reference),
-// and a duplicate must not survive because of that.
-// A rectangle with a side that is not > 0 (zero, negative, NaN) is not handed to the routine either -- its `inside` test passes every
-// point of the slab over a zero-length edge -- and matches nothing; a NaN position or heading leaves the routine < 3 vertices, a
-// zero ratio.  So a NaN or degenerate box ends as its own seed.
+// Two candidates whose five float32 numbers are equal (finite, non-zero area) overlap by 1 without asking the routine.  The routine
+// no longer needs that: it clips one rectangle in the other's frame and scores coincident, collinear, half-turned and one-ulp-apart
+// rectangles by their exact overlap (rotate_iou.hip; the reference's vertex collection, which it used to mirror, passed or failed
+// corners on coincident edges by rounding).  The shortcut stays as the contract of include/monosowa_kitti.h states it.
+// A rectangle with a side that is not > 0 (zero, negative, NaN) is not handed to the routine either, which would return 0 for it,
+// and matches nothing; a NaN position or heading leaves the routine without a vertex, a zero ratio.  So a NaN or degenerate box
+// ends as its own seed.
 namespace fuse {
 
 constexpr int kThreads = 512;

@@ -2,10 +2,14 @@
 // box IoU, N x K pairs per call.  Replaces the numba-CUDA kernel of
 // lib/datasets/kitti/kitti_eval_python/rotate_iou.py:263-330 (+ the CPU loop eval.py:197-223 for the 3D case).
 //
-// Same definition as the reference: the intersection polygon's vertices are the corners of either rectangle that lie
-// inside the other plus the pairwise edge intersections; they are ordered around their centroid and the polygon is
-// summed as a triangle fan.  One thread per (box, query) pair, the 64 x 64 tile's boxes staged in LDS, everything in
-// registers (at most 24 candidate vertices); pure f32 like the reference.
+// Same quantity as the reference -- the area of the intersection of two rotated rectangles, combined by `criterion` -- but NOT its
+// vertex collection (corners kept by >= tests on absolute coordinates, edge crossings divided by a determinant that vanishes for
+// parallel edges, a sort by pseudo-angle): that scheme returns 0, 1/3, values far above 1 or NaN on identical, collinear, half-turned
+// and one-ulp-apart boxes, and loses digits on absolute coordinates at KITTI distances.  Here box 2 is expressed in box 1's frame
+// (centre difference, heading difference), its four corners are clipped against box 1's four axis-aligned sides
+// (Sutherland-Hodgman, at most 8 vertices) and the polygon is summed as a fan about its first vertex.  Every inside / outside test is
+// taken on a coordinate relative to box 1, every divisor is the distance between a point inside and a point outside, and coincident
+// and edge-sharing boxes score their exact overlap.  One thread per (box, query) pair, the 64 x 64 tile's boxes staged in LDS; pure f32.
 #include <hip/hip_runtime.h>
 
 #include "../../include/monosowa_kitti.h"
@@ -14,83 +18,64 @@ namespace kitti {
 
 struct P2 { float x, y; };
 
-__device__ __forceinline__ void corners_of(const float *b, P2 c[4]) {
-  // (cx, cy, w, h, angle): corners (-w/2,-h/2), (-w/2,h/2), (w/2,h/2), (w/2,-h/2) rotated clockwise by angle
-  const float ca = cosf(b[4]), sa = sinf(b[4]);
-  const float hx = b[2] * 0.5f, hy = b[3] * 0.5f;
-  const float xs[4] = {-hx, -hx, hx, hx}, ys[4] = {-hy, hy, hy, -hy};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    c[i].x = ca * xs[i] + sa * ys[i] + b[0];
-    c[i].y = -sa * xs[i] + ca * ys[i] + b[1];
-  }
-}
+constexpr int kMaxVerts = 8;             // a quadrilateral gains at most one vertex per clipping side
 
-__device__ __forceinline__ bool inside(P2 p, const P2 q[4]) {          // projections on two adjacent edges of q
-  const float abx = q[1].x - q[0].x, aby = q[1].y - q[0].y, adx = q[3].x - q[0].x, ady = q[3].y - q[0].y;
-  const float apx = p.x - q[0].x, apy = p.y - q[0].y;
-  const float abab = abx * abx + aby * aby, abap = abx * apx + aby * apy;
-  const float adad = adx * adx + ady * ady, adap = adx * apx + ady * apy;
-  return abab >= abap && abap >= 0.f && adad >= adap && adap >= 0.f;
-}
-
-__device__ __forceinline__ bool cross_point(P2 A, P2 B, P2 C, P2 D, P2 &out) {   // segments AB x CD (proper crossing)
-  const float bax = B.x - A.x, bay = B.y - A.y, dax = D.x - A.x, cax = C.x - A.x, day = D.y - A.y, cay = C.y - A.y;
-  const bool acd = day * cax > cay * dax;
-  const bool bcd = (D.y - B.y) * (C.x - B.x) > (C.y - B.y) * (D.x - B.x);
-  if (acd == bcd) return false;
-  const bool abc = cay * bax > bay * cax, abd = day * bax > bay * dax;
-  if (abc == abd) return false;
-  const float dcx = D.x - C.x, dcy = D.y - C.y;
-  const float abba = A.x * B.y - B.x * A.y, cddc = C.x * D.y - D.x * C.y;
-  const float dh = bay * dcx - bax * dcy;
-  out.x = (abba * dcx - bax * cddc) / dh;
-  out.y = (abba * dcy - bay * cddc) / dh;
-  return true;
-}
-
-__device__ float intersection_area(const float *b1, const float *b2) {
-  P2 c1[4], c2[4], v[24];
-  corners_of(b1, c1);
-  corners_of(b2, c2);
-  int n = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if (inside(c1[i], c2)) v[n++] = c1[i];
-    if (inside(c2[i], c1)) v[n++] = c2[i];
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      P2 t;
-      if (cross_point(c1[i], c1[(i + 1) & 3], c2[j], c2[(j + 1) & 3], t)) v[n++] = t;
-    }
-  if (n < 3) return 0.f;
-  // order around the centroid by a monotone pseudo-angle: x / |v| for the upper half plane, -2 - x / |v| below
-  float cx = 0.f, cy = 0.f;
-  for (int i = 0; i < n; ++i) { cx += v[i].x; cy += v[i].y; }
-  cx /= n; cy /= n;
-  float key[24];
+// The part of the convex polygon in[0..n) with s * c <= lim, c its x (AXIS 0) or y (AXIS 1) coordinate and s = +-1.  A vertex on the
+// side is inside.  A crossing lies between a vertex inside and one outside, so sp and sq differ in sign and sp - sq is at least as
+// large as either; its clipped coordinate is the side's own, not an interpolation.
+template <int AXIS>
+__device__ __forceinline__ int clip_side(const P2 *in, int n, P2 *out, float s, float lim) {
+  int m = 0;
   for (int i = 0; i < n; ++i) {
-    const float dx = v[i].x - cx, dy = v[i].y - cy;
-    const float d = sqrtf(dx * dx + dy * dy);
-    float k = dx / d;
-    if (dy / d < 0.f) k = -2.f - k;
-    key[i] = k;
+    const P2 p = in[i], q = in[i + 1 == n ? 0 : i + 1];
+    const float sp = lim - s * (AXIS ? p.y : p.x), sq = lim - s * (AXIS ? q.y : q.x);
+    const bool p_in = sp >= 0.f, q_in = sq >= 0.f;
+    if (p_in && m < kMaxVerts) out[m++] = p;
+    if (p_in != q_in && m < kMaxVerts) {
+      const float t = sp / (sp - sq);
+      P2 r;
+      if (AXIS) {
+        r.x = p.x + t * (q.x - p.x);
+        r.y = s * lim;
+      } else {
+        r.x = s * lim;
+        r.y = p.y + t * (q.y - p.y);
+      }
+      out[m++] = r;
+    }
   }
-  for (int i = 1; i < n; ++i) {                         // insertion sort (n <= 24, usually <= 8)
-    const float k = key[i];
-    const P2 p = v[i];
-    int j = i;
-    while (j > 0 && key[j - 1] > k) { key[j] = key[j - 1]; v[j] = v[j - 1]; --j; }
-    key[j] = k;
-    v[j] = p;
+  return m;
+}
+
+// b = (cx, cy, w, h, angle): corners (-w/2,-h/2), (-w/2,h/2), (w/2,h/2), (w/2,-h/2) rotated clockwise by angle, as the reference has
+// them.  A box with a side that is not > 0 (zero, negative, NaN) has no area to share: 0.  A NaN or infinite centre or heading fails
+// every >= test and leaves no vertex: 0 as well.
+__device__ float intersection_area(const float *b1, const float *b2) {
+  if (!(b1[2] > 0.f && b1[3] > 0.f && b2[2] > 0.f && b2[3] > 0.f)) return 0.f;
+  const float ca = cosf(b1[4]), sa = sinf(b1[4]);
+  const float d = b2[4] - b1[4];                           // equal headings: cos, sin = 1, 0 exactly
+  const float cd = cosf(d), sd = sinf(d);
+  const float dx = b2[0] - b1[0], dy = b2[1] - b1[1];
+  const float ox = ca * dx - sa * dy, oy = sa * dx + ca * dy;      // box 2's centre in box 1's frame
+  const float hx = b2[2] * 0.5f, hy = b2[3] * 0.5f;
+  const float xs[4] = {-hx, -hx, hx, hx}, ys[4] = {-hy, hy, hy, -hy};
+  P2 u[kMaxVerts], v[kMaxVerts];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    u[i].x = cd * xs[i] + sd * ys[i] + ox;
+    u[i].y = -sd * xs[i] + cd * ys[i] + oy;
   }
-  float area = 0.f;
-  for (int i = 0; i < n - 2; ++i)
-    area += fabsf(((v[0].x - v[i + 2].x) * (v[i + 1].y - v[i + 2].y) - (v[0].y - v[i + 2].y) * (v[i + 1].x - v[i + 2].x)) * 0.5f);
-  return area;
+  const float lx = b1[2] * 0.5f, ly = b1[3] * 0.5f;
+  int n = clip_side<0>(u, 4, v, 1.f, lx);
+  n = clip_side<0>(v, n, u, -1.f, lx);
+  n = clip_side<1>(u, n, v, 1.f, ly);
+  n = clip_side<1>(v, n, u, -1.f, ly);
+  if (n < 3) return 0.f;
+  float twice = 0.f;                                       // shoelace fan about vertex 0, on differences from it
+  for (int i = 1; i + 1 < n; ++i)
+    twice += (u[i].x - u[0].x) * (u[i + 1].y - u[0].y) - (u[i].y - u[0].y) * (u[i + 1].x - u[0].x);
+  const float area = fabsf(twice) * 0.5f;
+  return area < INFINITY ? area : 0.f;                     // (a NaN compares false)
 }
 
 __device__ __forceinline__ float ratio(float inter, float a1, float a2, int criterion) {

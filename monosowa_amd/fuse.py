@@ -15,8 +15,8 @@ view does not confirm keeps half of it), ``count`` per image and ``support`` = m
 
 The host function clips the rectangles in float64 (one rectangle's corners in the other's frame, clipped against its four sides)
 where the kernel runs the evaluation's float32 routine: the two agree on every pair whose IoU is not within the float32 routine's
-error of the threshold.  Where that routine is degenerate both follow one rule: a rectangle with a side that is not > 0 overlaps
-nothing, and two rectangles with the same five float32 numbers overlap by 1.
+error of the threshold (the routine clips the same way, in float32).  On degenerate input both follow one rule: a rectangle with a
+side that is not > 0 overlaps nothing, and two rectangles with the same five float32 numbers overlap by 1.
 """
 import numpy as np
 import torch

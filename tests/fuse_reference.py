@@ -220,6 +220,50 @@ def kernel_case(K, views, iou, first_seed=0):
     raise AssertionError("no seed in 200 keeps every pair %g away from the threshold" % MARGIN)
 
 
+TWIN_KINDS = ("ulp x", "ulp z", "ulp l", "ulp w", "ulp ry", "half turn", "collinear", "shorter")
+
+
+@functools.lru_cache(maxsize=None)
+def twin_case(iou=0.7, seed=0):
+    """One view, K = 16, images 0 and 2 full, image 1 empty: per image eight same-class pairs 20 m and more from each other, the
+    second of a pair being the first with (TWIN_KINDS) one float32 BEV number moved by one ulp, the heading turned by float32 pi,
+    the centre moved 0.2 m along the length (collinear long sides, IoU (l - 0.2) / (l + 0.2)), the length x 0.9 (IoU 0.9).  The
+    five BEV numbers of every row are float32 values, so the kernel's cast keeps them.  Every pair's exact IoU is above ``iou``
+    by more than MARGIN: each must end as ONE cluster of two.  -> the dict of kernel_case."""
+    rng = np.random.default_rng(seed)
+    f32 = lambda v: float(np.float32(v))
+    K, views, images = 16, 1, []
+    for b in range(3):
+        g, items = GEOM[b], []
+        for k, kind in enumerate(TWIN_KINDS if b != 1 else ()):
+            first = _row(rng, g, k % 3, f32(-30 + 20 * (k % 4) + rng.uniform(-2, 2)), f32(15 + 25 * (k // 4) + rng.uniform(-2, 2)),
+                         f32(rng.uniform(3.2, 4.6)), f32(rng.uniform(1.5, 2.0)), rng.uniform(-3, 3), 0.9 - 0.02 * k)
+            first[12] = f32(rng.uniform(-3, 3))
+            twin = list(first)
+            twin[13] = 0.5 - 0.02 * k
+            if kind.startswith("ulp"):
+                col = BEV[("x", "z", "l", "w", "ry").index(kind[4:])]
+                twin[col] = float(np.nextafter(np.float32(first[col]), np.float32(np.inf if rng.integers(0, 2) else -np.inf)))
+            elif kind == "half turn":
+                twin[12] = float(np.float32(first[12]) + np.float32(np.pi))
+            elif kind == "collinear":                                      # l is the rectangle's first side: its axis is (cos ry, -sin ry)
+                twin[9], twin[11] = f32(first[9] + 0.2 * math.cos(first[12])), f32(first[11] - 0.2 * math.sin(first[12]))
+            else:
+                twin[8] = f32(first[8] * 0.9)
+            assert all(float(np.float32(r[c])) == r[c] for r in (first, twin) for c in BEV) and twin != first
+            items += [(0, k, first), (0, k, twin)]
+        images.append(items)
+    rows, count, labels = _assemble(images, K, views)
+    per_image = []
+    for b in range(3):
+        ids, cands = candidates(rows, count, GEOM, b, views)
+        ious = same_class_ious(cands)
+        assert all(v - iou > MARGIN or v < iou - MARGIN for v in ious.values())
+        assert all(ious[(2 * k, 2 * k + 1)] - iou > MARGIN for k in range(len(ids) // 2))
+        per_image.append({"ids": ids, "cands": cands, "ious": ious, "labels": labels[b]})
+    return {"rows": rows, "count": count, "geom": GEOM.copy(), "images": per_image, "tries": 1, "K": K, "views": views, "iou": iou}
+
+
 def in_cluster_split(case):
     """(pairs of one generated cluster above the threshold, below it) over the case's same-class pairs."""
     above = below = 0

@@ -51,6 +51,26 @@ def test_host_fuse_equals_the_restatement(K, views, mode):
     assert count[1] == 0
 
 
+@pytest.mark.parametrize("mode", ["seed", "mean"])
+def test_near_twin_scene_merges_every_pair(mode):
+    """FR.twin_case, the scene of the kernel test: every pair's oracle IoU is above the threshold, the restatement and the host
+    function make one cluster of two of each."""
+    from monosowa_amd.fuse import fuse_rows_host
+    case = FR.twin_case()
+    pairs = len(FR.TWIN_KINDS)
+    assert case["count"].tolist() == [2 * pairs, 0, 2 * pairs]
+    rows, count, support = fuse_rows_host(case["rows"], case["count"], case["geom"], case["iou"], mode, 1)
+    for b, (seeds, want, members) in enumerate(FR.reference(case, mode)):
+        img = case["images"][b]
+        n = len(seeds)
+        assert n == len(img["ids"]) // 2 and members.tolist() == [2] * n
+        assert not any(img["cands"][2 * k, FR.BEV].tobytes() == img["cands"][2 * k + 1, FR.BEV].tobytes() for k in range(n))
+        assert count[b] == n and support[b, :n].tolist() == members.tolist()
+        np.testing.assert_allclose(rows[b, :n], want, rtol=0, atol=1e-9, equal_nan=True)
+    above = [case["images"][0]["ious"][(2 * k, 2 * k + 1)] for k in range(pairs)]
+    assert min(above[:6]) > 0.999 and abs(above[7] - 0.9) < 1e-6 and 0.85 < above[6] < 0.93, above
+
+
 def test_unmirror_inverts_the_mirror_map():
     """Rows mirrored with the inverse map (u -> W - u, calibration unchanged) come back to within 1e-9: double arithmetic on
     magnitudes up to 1e4 over a few operations rounds at about 1e-12."""

@@ -85,6 +85,20 @@ def test_fuse_kernel_equals_the_restatement(K, views, mode):
 
 
 @pytest.mark.parametrize("mode", ["seed", "mean"])
+def test_fuse_kernel_merges_near_twins_as_the_restatement_does(mode):
+    """Pairs one ulp apart, turned by float32 pi, collinear and of the same width (FR.twin_case): no two rows are bit-equal, so
+    every flag comes from the overlap routine, and each pair must end as one cluster of two."""
+    case = FR.twin_case()
+    rows, count, support = _device_fuse(case, mode)
+    for b, want in enumerate(FR.reference(case, mode)):
+        img = case["images"][b]
+        pairs = len(img["ids"]) // 2
+        assert [img["labels"][q] for q in want[0]] == list(range(pairs)) and want[2].tolist() == [2] * pairs, (b, want[0], want[2])
+        _assert_image(rows[b], count[b], support[b], img, case["K"], want, mode, ("twins", mode, b))
+    assert count.tolist() == [len(FR.TWIN_KINDS), 0, len(FR.TWIN_KINDS)]
+
+
+@pytest.mark.parametrize("mode", ["seed", "mean"])
 def test_fuse_kernel_writes_the_same_bytes_wherever_the_buffers_lie(mode):
     case = FR.kernel_case(50, 2, 0.5)
     first = _device_fuse(case, mode, offset=0)

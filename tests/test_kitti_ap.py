@@ -146,13 +146,18 @@ def test_written_results_round_trip_through_the_label_reader(ap, tmp_path, monke
 @pytest.mark.gpu
 @pytest.mark.parametrize("criterion", [-1, 0, 1, 2])
 def test_rotate_iou_kernel_equals_the_reference_device_function(golden_dir, criterion):
-    """The HIP kernel behind rotate_iou_gpu_eval against the reference's own device function (non-degenerate pairs)."""
+    """The HIP kernel behind rotate_iou_gpu_eval against the reference's own device function.  On the 8 exactly identical pairs the
+    fixture records the reference's 0 or 1/3; the kernel must give the exact answer there: 1, or the area for criterion 2."""
     from monosowa_amd import kitti_eval as K
     r = np.load(os.path.join(golden_dir, "kitti_rotate_iou.npz"))
     same = (r["boxes"][:, None, :] == r["qboxes"][None, :, :]).all(-1)
     got = K.rotate_iou_gpu_eval(r["boxes"], r["qboxes"], criterion)
     ref = r["iou_crit%d" % criterion]
     assert np.abs(got - ref)[~same].max() <= 2e-5 * max(1.0, ref.max()), np.abs(got - ref)[~same].max()
+    assert same.sum() == 8 and np.isfinite(got).all()
+    rows = np.nonzero(same)[0]
+    exact = r["boxes"][rows, 2] * r["boxes"][rows, 3] if criterion == 2 else np.ones(8, dtype=np.float32)      # the float32 product
+    assert np.array_equal(got[same], exact), (got[same], exact)
 
 
 @pytest.mark.gpu
