@@ -58,6 +58,30 @@ int mono_decode_dets_f64(const float *dets, const double *geom, const double *cl
 int mono_fuse_dets_f64(const double *rows, const int *count, const double *geom, double iou, int mode, double *out_rows,
                        int *out_count, int *out_support, int B, int K, int V, void *stream);
 
+/* The inverse of mono_decode_dets_f64 for self-training: decoded (and fused) rows -> the padded target arrays the criterion reads,
+ * in the frame of the student's own flip and crop; one kernel, one wavefront per image, one lane per slot.
+ * rows f64 [B, R, 14], count int32 [B] (kept rows first), records f64 [B, 23] = (P2's 12 float32 values, img_w, img_h, flip,
+ * the six numbers of the crop's affine `trans`, crop_scale, canonical_scale), cls_mean_size f64 [C, 3].
+ * writelist_mask: bit c set when class c is trained on; depth_mode 0 'normal' (z * crop_scale), 1 'inverse' (z / crop_scale), 2 'none';
+ * weight_mode 0: label_weight = the row's score (0 for a score that is negative or not finite), 1: = weight.
+ * outputs: 17 device pointers (a host array), [B, max_objs, ...] each, in this order and with the dataset's dtypes: labels int8,
+ * boxes f32 [4], boxes_3d f32 [6], depth f32 [1], size_2d f32 [2], size_3d f32 [3], src_size_3d f32 [3], heading_bin int64 [1],
+ * heading_res f32 [1], mask_2d bool, calibs f32 [3, 4], indices int64, objects f32 [7], label_weight f32, ignore_boxes f32 [4],
+ * ignore_mask bool, n_ignore int32 [B].  Every byte of every output is written.
+ * Slot i < min(count, R, max_objs) is line i of the label file write_kitti_results(..., dontcare_below=min_score) would write from the
+ * rows if it wrote every number exactly -- a row with !(score >= min_score), NaN included, as a DontCare line -- read by
+ * KITTI_Dataset.__getitem__ on a training split with label_weights 'score' and ignore_regions on under the record's flip and crop
+ * (aug_calib off): box2d and pos float32, truncation and occlusion 0, level UnKnown for !(y2 - y1 + 1 >= 25), the depth gate [2, 65]
+ * on the unscaled float32 z, the centre-inside test, the negative l / r / t / b rule with clip_2d, z *= canonical_scale before
+ * depth and objects, the heading recomputed in float32 from the flipped ry and box centre, every value rounded to its array's
+ * dtype; label_weight 1 behind the lines.  The ignore boxes (DontCare lines and writelist lines that end as no target; empty ones
+ * dropped) are packed at the front in line order, unused slots zero; n_ignore counts them.  rect_to_img's and affine_transform's
+ * products run left to right in double, each operation rounded (numpy hands them to BLAS); the heading's float32 atan2 is the
+ * double one rounded.  max_objs <= 64, C <= 31; otherwise -2. */
+int mono_encode_targets_f64(const double *rows, const int *count, const double *records, const double *cls_mean_size,
+                            int writelist_mask, int depth_mode, int clip_2d, double min_score, int weight_mode, double weight,
+                            int res_w, int res_h, int B, int R, int C, int max_objs, void *const *outputs, void *stream);
+
 /* KITTI AP accumulation, HOST functions: the official matching protocol as kitti_eval_python/eval.py:234-410
  * runs it (numba there), one call per (class, difficulty, min_overlap) over all images.  Host pointers.
  *   n_gt / n_dt / n_dc [n_images]: boxes per image;   overlaps: the images' [n_dt, n_gt] matrices (row = detection), concatenated;

@@ -13,4 +13,7 @@ def __getattr__(name):
     if name == "LabelAudit":                # the per-label disagreement record (monosowa_amd/label_audit.py)
         from .label_audit import LabelAudit
         return LabelAudit
+    if name == "Teacher":                   # the mean-teacher path of the train loop (monosowa_amd/teacher.py)
+        from .teacher import Teacher
+        return Teacher
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

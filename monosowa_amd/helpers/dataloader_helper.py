@@ -40,3 +40,18 @@ def build_dataloader(cfg, workers=4, drop_last=False, test=True):
     test_loader = DataLoader(test_set, batch_size=cfg["batch_size"], num_workers=workers, worker_init_fn=my_worker_init_fn,
                              shuffle=False, pin_memory=torch.cuda.is_available(), drop_last=False, collate_fn=collate)
     return train_loader, test_loader
+
+
+def build_unlabelled_loader(cfg, workers=4):
+    """``dataset.unlabelled_split: NAME`` -> the loader of ``UnlabelledKITTI`` (monosowa_amd/kitti_dataset.py): raw frames with the
+    training sample's augmentation draws and no labels, for ``trainer.teacher``.  The train loader's arrangement: shuffled, the train
+    batch size, ``collate_raw``, and under torch.distributed a DistributedSampler of its own.  The short last batch of a pass is
+    dropped: every batch has one shape (one captured graph in the teacher's engine) and the same size on every rank."""
+    from ..image_prep import collate_raw
+    from ..kitti_dataset import UnlabelledKITTI
+    if cfg.get("type") != "KITTI":
+        raise ValueError("dataset.unlabelled_split reads a KITTI-format directory: dataset.type must be 'KITTI', got %r" % (cfg.get("type"),))
+    dataset = UnlabelledKITTI(cfg.get("unlabelled_split"), cfg)
+    sampler = DistributedSampler(dataset, shuffle=True) if is_dist_avail_and_initialized() and get_world_size() > 1 else None
+    return DataLoader(dataset, batch_size=cfg["batch_size"], num_workers=workers, worker_init_fn=my_worker_init_fn,
+                      shuffle=sampler is None, sampler=sampler, pin_memory=torch.cuda.is_available(), drop_last=True, collate_fn=collate_raw)

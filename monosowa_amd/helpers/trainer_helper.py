@@ -33,6 +33,14 @@ checkpoint naming.  Differences that do not change results:
   and rank 0 logs the number of labels seen and the median and maximum of their |d - d*|.  ``tools/label_audit.py report`` ranks the
   labels over the epochs.  Absent, None or false: nothing is built, allocated, launched, written or logged; the checkpoint is the same
   either way.
+* ``trainer.teacher: {...}`` (optional, absent from the shipped config; keys ``refresh``, ``source``, ``per_step``, ``min_score``,
+  ``weights``, ``start_epoch`` -- monosowa_amd/teacher.py): a mean teacher labels the raw frames of ``dataset.unlabelled_split`` one cycle
+  ahead, and from ``start_epoch`` on every optimizer step is one cycle of the K labelled loader batches followed by ``per_step``
+  pseudo-labelled ones, under ``train_cycle``'s rules for the whole cycle.  At the top of a cycle: collect the batches submitted
+  during the previous cycle (the only wait: a slot event recorded before that cycle's kernels), refresh the teacher's weights when
+  ``refresh`` optimizer steps have passed (the first cycle of a run refreshes), submit the next cycle's batches, run the cycle.  The
+  ``Teacher`` is built by the caller from the whole configuration and handed over as ``teacher=``.  Absent or None: nothing is built,
+  allocated, launched or logged; nothing is added to a checkpoint either way.
 """
 import contextlib
 import math
@@ -106,7 +114,7 @@ def stage_batch(raw, device):
 
 class Trainer(object):
     def __init__(self, cfg, model, optimizer, train_loader, test_loader, lr_scheduler, warmup_lr_scheduler,
-                 logger, loss, model_name):
+                 logger, loss, model_name, teacher=None):
         self.cfg = cfg
         self.optimizer = optimizer
         self.train_loader = train_loader
@@ -141,6 +149,10 @@ class Trainer(object):
         self._history_fresh = not cfg.get("resume_model", None)      # the first write of this run truncates history.jsonl
         label_audit = self._label_audit_flag(cfg.get("label_audit"))
         self.label_audit = None          # LabelAudit with trainer.label_audit, built below on the device the model trains on
+        self.teacher_cfg = self._teacher_config(cfg.get("teacher"), ema_decay is not None, label_audit, teacher)
+        self.teacher = teacher           # monosowa_amd.Teacher with trainer.teacher, built by the caller from the whole configuration
+        self._teacher_cycles = 0         # cycles of this run with the teacher on: it refreshes when this is a multiple of `refresh`
+        self._pseudo_counts = (0, 0)     # (targets, ignore boxes) of the pseudo batches of the cycle collected last
 
         if cfg.get("pretrain_model"):
             assert os.path.exists(cfg["pretrain_model"])
@@ -162,6 +174,8 @@ class Trainer(object):
             from ..label_audit import LabelAudit
             self.label_audit = LabelAudit(self._label_audit_rows(train_loader), self.device)
             self.detr_loss.audit = self.label_audit
+        if self.teacher is not None:
+            self.teacher.bind_source(self.ema)
         if resume is not None:
             self.epoch, self.best_result, self.best_epoch = load_checkpoint(
                 model=self.model, optimizer=self.optimizer, filename=resume,
@@ -170,6 +184,13 @@ class Trainer(object):
             self.logger.info("Loading Checkpoint... Best Result:{}, Best Epoch:{}".format(self.best_result, self.best_epoch))
 
     def train(self):
+        try:
+            return self._train()
+        finally:
+            if self.teacher is not None:                   # in-flight batches, the engine's graphs, the unlabelled loader's workers
+                self.teacher.close()
+
+    def _train(self):
         start_epoch = self.epoch
         best_result, best_epoch = self.best_result, self.best_epoch
         main = misc.is_main_process()
@@ -253,6 +274,23 @@ class Trainer(object):
         if not isinstance(value, bool):
             raise ValueError("trainer.label_audit = %r is not a bool (absent, None or false: off)" % (value,))
         return value
+
+    @staticmethod
+    def _teacher_config(value, ema_on, label_audit, teacher):
+        """``trainer.teacher``: None for absent or None (off), else the checked ``TeacherConfig``; the key and the ``teacher=``
+        argument come together or not at all."""
+        if value is None:
+            if teacher is not None:
+                raise ValueError("Trainer(teacher=...) without trainer.teacher in the configuration")
+            return None
+        from ..teacher import teacher_config
+        checked = teacher_config(value, ema_on, getattr(teacher, "threshold", None))
+        if label_audit:
+            raise ValueError("trainer.label_audit names every label by its label line: pseudo rows have none, so it cannot be "
+                             "combined with trainer.teacher")
+        if teacher is None:
+            raise ValueError("trainer.teacher is set: build monosowa_amd.Teacher from the whole configuration and pass it as teacher=")
+        return checked
 
     @staticmethod
     def _label_audit_rows(train_loader):
@@ -397,7 +435,23 @@ class Trainer(object):
             return torch.clamp(t / ranks, min=1)[0]
         return max(n / ranks, 1.0)
 
-    def train_cycle(self, raws):
+    def _teacher_turn(self):
+        """The top of a cycle with the teacher on: the staged pseudo batches of THIS cycle (submitted during the previous one; none
+        in the first), then the refresh when it is due, then the next cycle's submissions."""
+        t, c = self.teacher, self.teacher_cfg
+        staged, targets, ignored = [], 0, 0
+        while t.in_flight():
+            staged.append(t.collect())
+            targets, ignored = targets + t.last_counts[0], ignored + t.last_counts[1]
+        self._pseudo_counts = (targets, ignored)           # of the whole cycle (per_step batches), from the pinned copies
+        if self._teacher_cycles % c.refresh == 0:
+            t.refresh()
+        self._teacher_cycles += 1
+        for _ in range(c.per_step):
+            t.submit(t.next_raw())
+        return staged
+
+    def train_cycle(self, raws, staged=()):
         """One optimizer step over the K = len(raws) collated loader batches of a cycle; returns the last micro-batch's (total loss
         tensor, loss dict).  Defined as one DDP step of K * W ranks (W the world size), rank by rank: every micro-batch has its own
         forward (its own matching and size compensation) and is normalised by the box count of the whole cycle over all ranks,
@@ -405,11 +459,13 @@ class Trainer(object):
         micro-batch order, one float32 add per element and micro-step; the optimizer (and its guard) sees the sum once.  Under DDP
         only the last backward all-reduces.  The staged copy of a batch lives for its own micro-step only.  With ``trainer.history`` the
         row of the cycle holds sum_k term_k / K for every raw loss term (``add_losses`` with scale 1 / K) and sum_k total_k for
-        ``loss_detr``: ``total`` carries its 1 / K already and is added as it is."""
-        K = len(raws)
-        if K == 1:                                         # the tail of an epoch: exactly a plain step
+        ``loss_detr``: ``total`` carries its 1 / K already and is added as it is.  ``staged`` (``trainer.teacher``): pseudo-labelled
+        micro-batches, already on the device, that follow the labelled ones as further micro-batches of the same cycle: K counts
+        them too."""
+        K = len(raws) + len(staged)
+        if K == 1 and not staged:                          # the tail of an epoch: exactly a plain step
             return self.train_step(*stage_batch(raws[0], self.device))
-        num_boxes = self._cycle_num_boxes(sum(self._host_box_count(raw) for raw in raws), K)
+        num_boxes = self._cycle_num_boxes(sum(self._host_box_count(raw) for raw in list(raws) + list(staged)), K)
         ddp = isinstance(self.model, torch.nn.parallel.DistributedDataParallel)
         if self._accumulator is None:
             from ..pointwise import GradAccumulator
@@ -419,8 +475,8 @@ class Trainer(object):
         acc.begin()
         weight_dict = self.detr_loss.weight_dict
         self.optimizer.zero_grad(set_to_none=True)
-        for k, raw in enumerate(raws):
-            inputs, calibs, targets, info = stage_batch(raw, self.device)
+        for k in range(K):
+            inputs, calibs, targets, info = stage_batch(raws[k], self.device) if k < len(raws) else staged[k - len(raws)]
             target_list = self.prepare_targets(targets, inputs.shape[0])
             if self.label_audit is not None:
                 self._audit_begin(targets, info, inputs.shape[0])
@@ -449,14 +505,17 @@ class Trainer(object):
             print(">>>>>>> Epoch:", str(epoch) + ":")
         bar = tqdm.tqdm(total=len(self.train_loader), leave=(self.epoch + 1 == self.cfg["max_epoch"]), desc="iters", disable=not main)
         steps = 0
-        if self.accum_steps > 1:
+        teaching = self.teacher is not None and epoch >= self.teacher_cfg.start_epoch
+        if self.accum_steps > 1 or teaching:
             raws = []
 
             def cycle():
                 nonlocal steps, raws
-                total, loss_dict = self.train_cycle(raws)
+                total, loss_dict = self.train_cycle(raws, self._teacher_turn()) if teaching else self.train_cycle(raws)
                 if steps % self.log_interval == 0:             # every log_interval-th optimizer step
                     self._log(steps, loss_dict)
+                    if teaching and misc.is_main_process():
+                        print("pseudo: targets %d, ignored %d\n" % self._pseudo_counts)
                 steps += 1
                 bar.update(len(raws))
                 raws = []

@@ -34,11 +34,12 @@ class Completed:
     """One finished batch: ``tag`` as given to ``submit``; ``dets`` float32 ``[B, K, 37]``, or, for a batch submitted with
     geometry, ``rows`` float64 ``[B, K, 14]`` (kept rows first) and ``count`` int32 ``[B]``; on an engine with ``fuse=`` the rows
     are the fused ones, ``[B, V * K, 14]``, and ``support`` int32 ``[B, V * K]`` holds the members of each row's cluster.  Host arrays
-    owned by the caller."""
-    __slots__ = ("tag", "dets", "rows", "count", "support")
+    owned by the caller.  ``extra``: None, or for a batch submitted with ``after=`` the dict that hook returned, its tensors as host
+    arrays."""
+    __slots__ = ("tag", "dets", "rows", "count", "support", "extra")
 
-    def __init__(self, tag, dets=None, rows=None, count=None, support=None):
-        self.tag, self.dets, self.rows, self.count, self.support = tag, dets, rows, count, support
+    def __init__(self, tag, dets=None, rows=None, count=None, support=None, extra=None):
+        self.tag, self.dets, self.rows, self.count, self.support, self.extra = tag, dets, rows, count, support, extra
 
 
 class _Graph:
@@ -114,20 +115,25 @@ class InferenceEngine:
         self.replays = self.eager_forwards = 0
 
     # ------------------------------------------------------------------------------------------------ the public calls
-    def submit(self, inputs, calibs, img_size, height_crop, prep=None, geom=None, tag=None):
+    def submit(self, inputs, calibs, img_size, height_crop, prep=None, geom=None, tag=None, after=None):
         """Enqueues one batch and returns the batches that have completed, oldest first (possibly none).  ``inputs``: a raw
         batch as ``collate_raw`` makes it (uint8 canvas; ``prep`` = its records) or prepared float32 images; ``calibs``
         ``[B, 3, 4]``; ``img_size`` ``[B, 2]`` and ``height_crop`` ``[B]`` as the loader's ``info`` carries them; ``geom``: float64
-        ``[B, 10]`` per-image geometry (kitti_eval.GEOM_DOUBLES) to have the rows decoded on the device."""
+        ``[B, 10]`` per-image geometry (kitti_eval.GEOM_DOUBLES) to have the rows decoded on the device.
+        ``after(rows, count, slot)`` (a batch with ``geom`` only): called once, behind the decode (and the fuse) and before the batch's
+        completion event is recorded, with the device rows -- the fused ones on an engine that fuses -- and the batch's ``_Slot``
+        (None on a CPU device).  It may enqueue launches on the current stream and copy into ``slot.pinned(name, like)`` buffers (names
+        of its own); the dict it returns comes back as ``Completed.extra``, tensors in it as host arrays.  Without it every launch
+        and byte is what it is without the argument."""
         self._raise_pending()
         done = []
         while len(self.queue) >= self.in_flight:                         # bounded: the oldest batch's event, nothing wider
             done.append(self._complete())
         try:
             if self.cuda:
-                self._enqueue(inputs, calibs, img_size, height_crop, prep, geom, tag)
+                self._enqueue(inputs, calibs, img_size, height_crop, prep, geom, tag, after)
             else:
-                self.queue.append(self._run_on_host(inputs, calibs, img_size, height_crop, prep, geom, tag))
+                self.queue.append(self._run_on_host(inputs, calibs, img_size, height_crop, prep, geom, tag, after))
         except Exception as e:               # the batches already in flight are delivered first; this surfaces at the next call
             self.error = e
         while self.queue and self._ready(self.queue[0]):
@@ -142,6 +148,11 @@ class InferenceEngine:
         while self.queue:
             done.append(self._complete())
         return done
+
+    def complete_oldest(self):
+        """The oldest batch in flight, waited for on its own event (None with nothing in flight); a failed ``submit`` raises first."""
+        self._raise_pending()
+        return self._complete() if self.queue else None
 
     def sync_weights(self):
         """Drops the captured graphs when the model's weights are no longer the ones they were captured from (optimizer steps,
@@ -190,11 +201,17 @@ class InferenceEngine:
         item = self.queue.popleft()
         if not self.cuda:
             return item
-        slot, tag, B, geom = item
+        slot, tag, B, geom, extra = item
         try:
             slot.done.synchronize()
             self.model_seconds += slot.start.elapsed_time(slot.end) * 1e-3
             self.images += B
+            if extra is not None:
+                done = Completed(tag, rows=slot.buffers["rows"][:B].numpy().copy(), count=slot.buffers["count"][:B].numpy().copy(),
+                                 extra=_host_copies(extra))
+                if geom == "fused":
+                    done.support = slot.buffers["support"][:B].numpy().copy()
+                return done
             if geom == "fused":
                 return Completed(tag, rows=slot.buffers["rows"][:B].numpy().copy(), count=slot.buffers["count"][:B].numpy().copy(),
                                  support=slot.buffers["support"][:B].numpy().copy())
@@ -284,9 +301,11 @@ class InferenceEngine:
         self.replays += 1
         return g.outputs
 
-    def _enqueue(self, inputs, calibs, img_size, height_crop, prep, geom, tag):
+    def _enqueue(self, inputs, calibs, img_size, height_crop, prep, geom, tag, after=None):
         if geom is not None and self.decode is None:
             raise ValueError("a batch with geometry needs InferenceEngine(decode=(cls_mean_size, threshold))")
+        _check_after(after, geom)
+        extra = None
         self._check_fuse(inputs, geom)
         flip = self.fuse is not None and self.fuse[1]
         kind = geom is not None
@@ -313,13 +332,19 @@ class InferenceEngine:
                 slot.pinned("count", count).copy_(count, non_blocking=True)
                 if support is not None:
                     slot.pinned("support", support).copy_(support, non_blocking=True)
+                if after is not None:
+                    if kind == "fuse on the host":
+                        raise ValueError("after= needs the fused rows on the device: more than %d candidates per image are fused on "
+                                         "the host" % MAX_CANDIDATES)
+                    extra = after(rows, count, slot)
+                    extra = {} if extra is None else extra
             else:
                 slot.pinned("dets", dets).copy_(dets, non_blocking=True)
             slot.done.record()
         except Exception:
             self.free_slots.append(slot)
             raise
-        self.queue.append((slot, tag, inputs.shape[0], kind))
+        self.queue.append((slot, tag, inputs.shape[0], kind, extra))
 
     def _check_fuse(self, inputs, geom):
         if self.fuse is None:
@@ -329,9 +354,10 @@ class InferenceEngine:
         if self.fuse[1] and not is_raw_batch(inputs):
             raise ValueError("tester.flip_tta mirrors raw frames (dataset.device_aug / the Detector); prepared float32 images cannot be mirrored")
 
-    def _run_on_host(self, inputs, calibs, img_size, height_crop, prep, geom, tag):
+    def _run_on_host(self, inputs, calibs, img_size, height_crop, prep, geom, tag, after=None):
         if geom is not None and self.decode is None:
             raise ValueError("a batch with geometry needs InferenceEngine(decode=(cls_mean_size, threshold))")
+        _check_after(after, geom)
         self._check_fuse(inputs, geom)
         images = prepare(inputs, prep, self.device) if is_raw_batch(inputs) else inputs.to(self.device)
         img_sizes = self._img_sizes(img_size, height_crop)
@@ -351,10 +377,25 @@ class InferenceEngine:
         if geom is None:
             return Completed(tag, dets=dets)
         rows, count = decode_rows_host(dets, geom.numpy(), self.decode[0].numpy(), self.decode[1])
-        if self.fuse is None:
-            return Completed(tag, rows=rows, count=count)
-        rows, count, support = fuse_rows_host(rows, count, geom.numpy()[:inputs.shape[0]], self.fuse[0], self.fuse[2], 2 if flip else 1)
-        return Completed(tag, rows=rows, count=count, support=support)
+        support = None
+        if self.fuse is not None:
+            rows, count, support = fuse_rows_host(rows, count, geom.numpy()[:inputs.shape[0]], self.fuse[0], self.fuse[2], 2 if flip else 1)
+        done = Completed(tag, rows=rows, count=count, support=support)
+        if after is not None:
+            extra = after(torch.from_numpy(rows), torch.from_numpy(count), None)
+            done.extra = _host_copies({} if extra is None else extra)
+        return done
+
+
+def _check_after(after, geom):
+    if after is not None and geom is None:
+        raise ValueError("after= is called with the decoded rows: the batch must come with geom")
+
+
+def _host_copies(extra):
+    """``Completed.extra`` of an ``after=`` hook's dict: host tensors (the slot's pinned buffers) as arrays of the caller's own,
+    everything else as it is."""
+    return {k: (v.numpy().copy() if isinstance(v, torch.Tensor) and not v.is_cuda else v) for k, v in extra.items()}
 
 
 class _Camera:

@@ -367,7 +367,9 @@ class KITTI_Dataset(data.Dataset):
         fx, fy, cx, cy = fx * s, fy * s, cx * s, cy * s
         return fx, fy, cx, cy, cy / (self.resolution[1] / 2.0)
 
-    def __getitem__(self, item):
+    def _draw_frame(self, item):
+        """The part of a sample that needs no label file: the image, the calibration, the augmentation draws from ``np.random`` (in
+        the reference's order) and ``info`` as far as the image decides it.  Shared by ``__getitem__`` and ``UnlabelledKITTI``."""
         index = int(self.idx_list[item])
         img = self.get_image(index)
         calib = self.get_calib(index)
@@ -406,9 +408,21 @@ class KITTI_Dataset(data.Dataset):
                 "canonical_scale": canonical_scale, "height_crop": height_cropped}
         if self.device_aug:
             info["prep"] = make_record(img_size, trans_inv, flipped, pd_record)
+        return index, img, calib, img_size, crop_scale, flipped, trans, trans_inv, info
+
+    def _augmentation_info(self, info, trans, trans_inv, crop_scale, calib, flipped):
+        """The entries a training / validation sample adds to ``info`` behind its targets."""
+        info.update({"affine": trans, "affine_inv": trans_inv, "scale_depth": crop_scale, "calib_P2": calib.P2, "calib_R0": calib.R0,
+                     "calib_V2C": calib.V2C, "resolution": self.resolution, "flip": flipped,
+                     "templates_dimensions": np.array([self.template_height, self.template_width, self.template_length], dtype=np.float32)})
+        return info
+
+    def __getitem__(self, item):
+        index, img, calib, img_size, crop_scale, flipped, trans, trans_inv, info = self._draw_frame(item)
         if self.split == "test":
             return img, calib.P2, img, info
 
+        canonical_scale = info["canonical_scale"]
         objects = self.get_label(index)
         if flipped:
             if self.aug_calib:
@@ -501,7 +515,41 @@ class KITTI_Dataset(data.Dataset):
             targets["label_weight"] = label_weight
         if self.ignore_regions:
             targets["ignore_boxes"], targets["ignore_mask"] = self._ignore_boxes([objects[i] for i in ignore_lines], trans)
-        info.update({"affine": trans, "affine_inv": trans_inv, "scale_depth": crop_scale, "calib_P2": calib.P2, "calib_R0": calib.R0,
-                     "calib_V2C": calib.V2C, "resolution": self.resolution, "flip": flipped,
-                     "templates_dimensions": np.array([self.template_height, self.template_width, self.template_length], dtype=np.float32)})
+        self._augmentation_info(info, trans, trans_inv, crop_scale, calib, flipped)
         return img, calib.P2, targets, info
+
+
+class UnlabelledKITTI(KITTI_Dataset):
+    """``dataset.unlabelled_split: NAME`` (optional; this project's): the frames of ``ImageSets/NAME.txt`` under ``training/`` as a
+    training ``KITTI_Dataset`` draws them -- the same ``np.random`` draws in the same order (photometric, flip, crop, scale, shifts) --
+    without their labels: ``[i] -> (raw uint8 [h, w, 3], P2, {"img_size"}, info)``, ``info`` the training sample's (``prep``,
+    ``affine``, ``scale_depth``, ``flip``, ``canonical_scale``, ...).  No label file is opened.  Needs ``dataset.device_aug: true``:
+    the frames feed a teacher that looks at them raw (monosowa_amd/teacher.py)."""
+
+    def __init__(self, split, cfg):
+        if not isinstance(split, str) or not split:
+            raise ValueError("dataset.unlabelled_split = %r is not the name of a file under ImageSets/" % (split,))
+        if cfg.get("device_aug") is not True:
+            raise ValueError("dataset.unlabelled_split needs dataset.device_aug: true (the teacher reads raw frames), got %r"
+                             % (cfg.get("device_aug"),))
+        self.root_dir = cfg.get("root_dir")
+        self.split = split
+        self._settings(cfg)
+        path = os.path.join(self.root_dir, "ImageSets", split + ".txt")
+        if not os.path.isfile(path):
+            raise ValueError("dataset.unlabelled_split: %s does not exist" % path)
+        with open(path) as f:
+            self.idx_list = [x.strip() for x in f.readlines()]
+        self.data_dir = os.path.join(self.root_dir, "training")
+        self.image_dir = os.path.join(self.data_dir, "image_2")
+        self.calib_dir = os.path.join(self.data_dir, "calib")
+        self.label_dir = None
+        self.data_augmentation = True
+
+    def get_label(self, idx):
+        raise RuntimeError("an unlabelled split has no label files")
+
+    def __getitem__(self, item):
+        index, img, calib, img_size, crop_scale, flipped, trans, trans_inv, info = self._draw_frame(item)
+        self._augmentation_info(info, trans, trans_inv, crop_scale, calib, flipped)
+        return img, calib.P2, {"img_size": img_size}, info

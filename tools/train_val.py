@@ -83,9 +83,14 @@ def main():
             print("Loading checkpoint from %s" % path)
             load_checkpoint(model, optimizer, path, device, logger)
 
+    teacher = {}
+    if cfg["trainer"].get("teacher") is not None:          # trainer.teacher: the mean teacher and its unlabelled loader, from the whole config
+        from monosowa_amd.helpers.dataloader_helper import build_unlabelled_loader
+        from monosowa_amd.teacher import Teacher
+        teacher = {"teacher": Teacher(cfg, model, device, loader=build_unlabelled_loader(cfg["dataset"], workers=args.workers))}
     trainer = Trainer(cfg=cfg["trainer"], model=model, optimizer=optimizer, train_loader=train_loader,
                       test_loader=test_loader, lr_scheduler=lr_scheduler, warmup_lr_scheduler=warmup_lr_scheduler,
-                      logger=logger, loss=loss, model_name=model_name)
+                      logger=logger, loss=loss, model_name=model_name, **teacher)
     tester = Tester(cfg=cfg["tester"], model=trainer.model, dataloader=test_loader, logger=logger,
                     train_cfg=cfg["trainer"], model_name=model_name)
     if cfg["dataset"]["test_split"] != "test":
