@@ -82,6 +82,40 @@ int mono_encode_targets_f64(const double *rows, const int *count, const double *
                             int writelist_mask, int depth_mode, int clip_2d, double min_score, int weight_mode, double weight,
                             int res_w, int res_h, int B, int R, int C, int max_objs, void *const *outputs, void *stream);
 
+/* The label memory of self-training (trainer.teacher_memory): one pass's rows of a frame merged into the rows remembered for it.
+ * rows f64 [B, R, 14] and count int32 [B] as mono_fuse_dets_f64 / mono_decode_dets_f64 leave them (the raw frame's coordinates);
+ * frame int32 [B]: the position of image b's frame in the bank, DISTINCT within a call (one workgroup owns one frame's block);
+ * bank f64 [N, M, 16] and bank_count int32 [N], updated in place.  Frame f holds k = clamp(bank_count[f], 0, M) entries of 16
+ * doubles: columns 0..13 a KITTI row in mono_decode_dets_f64's column order with column 13 the smoothed score, column 14 `hits`,
+ * column 15 `misses` (consecutive passes without a match).  Image b brings n = clamp(count[b], 0, R) rows in their order.
+ * w = 1.0 - momentum in double; everything in double, every operation rounded (no contraction).
+ *  1. Eligible: a row takes part only when its score is finite; the others are counted as `skipped` and otherwise ignored.
+ *  2. Flags: F[i][e] when row i and entry e have equal class (column 0 compared as double) and their BEV rectangles (x, z, l, w, ry;
+ *     rounded to float32) overlap by IoU >= (float)iou -- mono_fuse_dets_f64's test: the evaluation's intersection routine on (row,
+ *     entry) with criterion -1, compared in float32, a NaN never matches; two rectangles equal in all five float32 numbers, all five
+ *     finite, overlap by 1 without the routine (the shortcut fires for nothing else: an infinite or NaN number goes to the routine,
+ *     which finds no overlap); a rectangle with a side that is not > 0 matches nothing, an equal one included.
+ *  3. Walk, in row order: eligible row i claims the lowest-index unclaimed entry e with F[i][e], else it is unmatched.
+ *  4. Updates.  Claimed entry: columns 0..12 become the row's byte for byte; d = s_i - s; t = w * d; s' = s + t (three roundings);
+ *     hits += 1, misses = 0.  Unclaimed entry: d = 0.0 - s; t = w * d; s' = s + t; columns 0..12 and hits stay, misses += 1.
+ *     Unmatched eligible row: a candidate with columns 0..13 the row's byte for byte, hits = 1, misses = 0.
+ *  5. Drop: a candidate, old entry or new row, with !(s' >= drop_below) -- a NaN included -- is dropped.
+ *  6. Order: the survivors by s' descending; exact ties: old entries before new rows, old entries in slot order, new rows in row
+ *     order (ranked by counting).  The first M stay, the rest are evicted.
+ *  7. Writes: the frame's whole M x 16 block (survivors in order, zeros behind) and bank_count[f]; out_rows f64 [B, M, 14] = the
+ *     survivors' columns 0..13 in the same order, zeros behind; out_count int32 [B]; stats int32 [B, 6] = (matched: entries
+ *     claimed; created: unmatched eligible rows; missed: unclaimed entries; dropped; evicted; skipped), so that
+ *     k + created - dropped - evicted = out_count.  Blocks of frames the call does not name are not touched.
+ * A frame[b] outside [0, N): out_count 0, zero rows, zero stats, no bank access.
+ * It follows (P1) that on an empty block n <= M rows with finite scores >= drop_below in non-increasing order come back as they
+ * are, byte for byte, and (P3) that merging the same rows (sides > 0) again changes only `hits`: s - s is exactly 0 and every row's
+ * lowest unclaimed match is itself.  momentum -> 0 does not make s' = s_i (s + (s_i - s) rounds); 0 is outside the interval.
+ * Return: 0, -1 (NULL pointer), -2 (M not in 1..64, R not in 1..256, B or N negative, iou outside (0, 1], momentum outside (0, 1))
+ * or a hipError_t. */
+int mono_memory_merge_f64(const double *rows, const int *count, const int *frame, double *bank, int *bank_count, double momentum,
+                          double iou, double drop_below, double *out_rows, int *out_count, int *stats, int B, int R, int N, int M,
+                          void *stream);
+
 /* KITTI AP accumulation, HOST functions: the official matching protocol as kitti_eval_python/eval.py:234-410
  * runs it (numba there), one call per (class, difficulty, min_overlap) over all images.  Host pointers.
  *   n_gt / n_dt / n_dc [n_images]: boxes per image;   overlaps: the images' [n_dt, n_gt] matrices (row = detection), concatenated;

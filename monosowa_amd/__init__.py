@@ -16,4 +16,7 @@ def __getattr__(name):
     if name == "Teacher":                   # the mean-teacher path of the train loop (monosowa_amd/teacher.py)
         from .teacher import Teacher
         return Teacher
+    if name == "LabelMemory":               # the label memory of self-training (monosowa_amd/teacher_memory.py)
+        from .teacher_memory import LabelMemory
+        return LabelMemory
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

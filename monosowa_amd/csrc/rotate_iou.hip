@@ -328,4 +328,5 @@ int mono_box3d_overlap_f32(const float *boxes, const float *query, float *out, l
 
 #include "fuse_dets.h"     // duplicate suppression / flip-view fusion of the decoded rows (mono_fuse_dets_f64)
 #include "encode_targets.h" // decoded rows -> the dataset's padded training targets (mono_encode_targets_f64)
+#include "memory_merge.h"  // a pass's rows merged into the frame's remembered rows (mono_memory_merge_f64)
 #include "kitti_ap.h"     // host-side AP accumulation of the same library (mono_kitti_tp_scores_f64, mono_kitti_pr_f64)

@@ -1,7 +1,8 @@
 """Checkpoint dictionary {'epoch','model_state','optimizer_state','best_result','best_epoch'} saved
 as '<name>.pth' (reference: lib/helpers/save_helper.py:6-45).  DataParallel / DDP wrappers are
 unwrapped on save so checkpoints are interchangeable with the reference's.  With a weight average (monosowa_amd/ema.py,
-``trainer.ema_decay``) a sixth key, 'ema_state' = ``ModelEMA.state_dict()``, rides along; without one the dictionary is the reference's."""
+``trainer.ema_decay``) a sixth key, 'ema_state' = ``ModelEMA.state_dict()``, rides along, and with ``trainer.teacher_memory`` a key 'teacher_memory' = ``LabelMemory.state_dict()``; without
+either the dictionary is the reference's."""
 import logging
 import os
 
@@ -20,7 +21,7 @@ def model_state_to_cpu(model_state):
     return out
 
 
-def get_checkpoint_state(model=None, optimizer=None, epoch=None, best_result=None, best_epoch=None, ema=None):
+def get_checkpoint_state(model=None, optimizer=None, epoch=None, best_result=None, best_epoch=None, ema=None, memory=None):
     optim_state = optimizer.state_dict() if optimizer is not None else None
     if model is None:
         model_state = None
@@ -35,6 +36,8 @@ def get_checkpoint_state(model=None, optimizer=None, epoch=None, best_result=Non
         if model is not None and unwrap(model) is not model:
             ema_state["module"] = model_state_to_cpu(ema_state["module"])
         state["ema_state"] = ema_state
+    if memory is not None:                   # trainer.teacher_memory: the label memory (LabelMemory.state_dict(), N * M * 128 bytes)
+        state["teacher_memory"] = memory.state_dict()
     return state
 
 
@@ -42,10 +45,11 @@ def save_checkpoint(state, filename):
     torch.save(state, "{}.pth".format(filename))
 
 
-def load_checkpoint(model, optimizer, filename, map_location, logger=None, ema=None, weights="model"):
+def load_checkpoint(model, optimizer, filename, map_location, logger=None, ema=None, weights="model", memory=None):
     """``weights="ema"``: ``model`` receives the checkpoint's averaged weights (``ema_state["module"]``) instead of ``model_state``;
     KeyError when the file has none.  ``ema`` (a ``ModelEMA`` over ``model``): restored from ``ema_state``; from a checkpoint
-    without one it starts over from the loaded weights (``updates = 0``), with one warning."""
+    without one it starts over from the loaded weights (``updates = 0``), with one warning.  ``memory`` (a ``LabelMemory``): restored
+    from ``teacher_memory``; from a checkpoint without one, or with one of other frames, it starts empty, with one warning."""
     if weights not in ("model", "ema"):
         raise ValueError("load_checkpoint: weights must be 'model' or 'ema', got %r" % (weights,))
     if not os.path.isfile(filename):
@@ -70,6 +74,8 @@ def load_checkpoint(model, optimizer, filename, map_location, logger=None, ema=N
             ema.reset()
             (logger or logging.getLogger(__name__)).warning(
                 "checkpoint '%s' has no 'ema_state': the weight average starts from the loaded weights with updates = 0", filename)
+    if memory is not None:
+        memory.load_state_dict(checkpoint.get("teacher_memory"), logger)
     if optimizer is not None and checkpoint["optimizer_state"] is not None:
         optimizer.load_state_dict(checkpoint["optimizer_state"])
     if logger is not None:

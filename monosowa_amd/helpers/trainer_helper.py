@@ -41,6 +41,9 @@ checkpoint naming.  Differences that do not change results:
   ``refresh`` optimizer steps have passed (the first cycle of a run refreshes), submit the next cycle's batches, run the cycle.  The
   ``Teacher`` is built by the caller from the whole configuration and handed over as ``teacher=``.  Absent or None: nothing is built,
   allocated, launched or logged; nothing is added to a checkpoint either way.
+* ``trainer.teacher_memory: {...}`` (optional sibling of ``trainer.teacher``; keys ``momentum``, ``iou``, ``drop_below``, ``slots`` --
+  monosowa_amd/teacher_memory.py): that Teacher keeps a per-frame label memory on the device and encodes the memory's rows; the pseudo
+  log line gains the memory's tallies and every checkpoint the key ``teacher_memory``.  Absent or None: nothing of this.
 """
 import contextlib
 import math
@@ -153,6 +156,10 @@ class Trainer(object):
         self.teacher = teacher           # monosowa_amd.Teacher with trainer.teacher, built by the caller from the whole configuration
         self._teacher_cycles = 0         # cycles of this run with the teacher on: it refreshes when this is a multiple of `refresh`
         self._pseudo_counts = (0, 0)     # (targets, ignore boxes) of the pseudo batches of the cycle collected last
+        self._memory_counts = None       # trainer.teacher_memory: that cycle's (matched, created, missed, dropped, evicted) sums
+        if cfg.get("teacher_memory") is not None and self.teacher_cfg is None:
+            from ..teacher_memory import memory_config
+            memory_config(cfg["teacher_memory"], None)     # malformed, or the key without trainer.teacher: ValueError
 
         if cfg.get("pretrain_model"):
             assert os.path.exists(cfg["pretrain_model"])
@@ -179,7 +186,7 @@ class Trainer(object):
         if resume is not None:
             self.epoch, self.best_result, self.best_epoch = load_checkpoint(
                 model=self.model, optimizer=self.optimizer, filename=resume,
-                map_location=self.device, logger=self.logger, ema=self.ema)
+                map_location=self.device, logger=self.logger, ema=self.ema, **self._memory_argument())
             self.lr_scheduler.last_epoch = self.epoch - 1
             self.logger.info("Loading Checkpoint... Best Result:{}, Best Epoch:{}".format(self.best_result, self.best_epoch))
 
@@ -229,10 +236,16 @@ class Trainer(object):
         self.logger.info("Best Result:{}, epoch:{}".format(best_result, best_epoch))
         return None
 
+    def _memory_argument(self):
+        """``{"memory": the teacher's LabelMemory}`` with ``trainer.teacher_memory``, else nothing: the calls are today's."""
+        memory = getattr(self.teacher, "memory", None)
+        return {} if memory is None else {"memory": memory}
+
     def _checkpoint_state(self, best_result, best_epoch):
         if self.ema is None:
-            return get_checkpoint_state(self.model, self.optimizer, self.epoch, best_result, best_epoch)
-        return get_checkpoint_state(self.model, self.optimizer, self.epoch, best_result, best_epoch, ema=self.ema)
+            return get_checkpoint_state(self.model, self.optimizer, self.epoch, best_result, best_epoch, **self._memory_argument())
+        return get_checkpoint_state(self.model, self.optimizer, self.epoch, best_result, best_epoch, ema=self.ema,
+                                    **self._memory_argument())
 
     def _evaluate(self):
         """The tester's pass after an epoch; with the weight average on, over the averaged weights: the tester's model is swapped for
@@ -440,10 +453,14 @@ class Trainer(object):
         in the first), then the refresh when it is due, then the next cycle's submissions."""
         t, c = self.teacher, self.teacher_cfg
         staged, targets, ignored = [], 0, 0
+        remembered = None if getattr(t, "memory", None) is None else [0] * 5
         while t.in_flight():
             staged.append(t.collect())
             targets, ignored = targets + t.last_counts[0], ignored + t.last_counts[1]
+            if remembered is not None:
+                remembered = [a + b for a, b in zip(remembered, t.last_memory)]
         self._pseudo_counts = (targets, ignored)           # of the whole cycle (per_step batches), from the pinned copies
+        self._memory_counts = None if remembered is None else tuple(remembered)
         if self._teacher_cycles % c.refresh == 0:
             t.refresh()
         self._teacher_cycles += 1
@@ -515,7 +532,10 @@ class Trainer(object):
                 if steps % self.log_interval == 0:             # every log_interval-th optimizer step
                     self._log(steps, loss_dict)
                     if teaching and misc.is_main_process():
-                        print("pseudo: targets %d, ignored %d\n" % self._pseudo_counts)
+                        line = "pseudo: targets %d, ignored %d" % self._pseudo_counts
+                        if self._memory_counts is not None:
+                            line += ", memory: matched %d, created %d, missed %d, dropped %d, evicted %d" % self._memory_counts
+                        print(line + "\n")
                 steps += 1
                 bar.update(len(raws))
                 raws = []

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 _PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmonosowa_kitti.so")
-SYMBOLS = ("mono_rotate_iou_f32", "mono_box3d_overlap_f32", "mono_extract_dets_f32", "mono_decode_dets_f64", "mono_fuse_dets_f64", "mono_encode_targets_f64", "mono_kitti_tp_scores_f64", "mono_kitti_pr_f64")
+SYMBOLS = ("mono_rotate_iou_f32", "mono_box3d_overlap_f32", "mono_extract_dets_f32", "mono_decode_dets_f64", "mono_fuse_dets_f64", "mono_encode_targets_f64", "mono_memory_merge_f64", "mono_kitti_tp_scores_f64", "mono_kitti_pr_f64")
 _lib = None
 
 
@@ -45,6 +45,8 @@ def load():
         lib.mono_fuse_dets_f64.argtypes = [P] * 3 + [D, I] + [P] * 3 + [I] * 3 + [P]
         lib.mono_encode_targets_f64.restype = I
         lib.mono_encode_targets_f64.argtypes = [P] * 4 + [I] * 3 + [D, I, D] + [I] * 6 + [P, P]
+        lib.mono_memory_merge_f64.restype = I
+        lib.mono_memory_merge_f64.argtypes = [P] * 5 + [D] * 3 + [P] * 3 + [I] * 4 + [P]
         lib.mono_kitti_tp_scores_f64.restype = I
         lib.mono_kitti_tp_scores_f64.argtypes = [LL] + [P] * 9 + [I, D, P, P]
         lib.mono_kitti_pr_f64.restype = I

@@ -363,6 +363,22 @@ class Teacher:
         self.refreshes = 0
         self.last_counts = (0, 0)                    # (targets, ignore boxes) of the batch collected last, from the pinned copies
         self.last_rows = None                        # (rows, count) that batch was encoded from: the engine's host copies
+        # trainer.teacher_memory (monosowa_amd/teacher_memory.py): the rows are merged into the frame's remembered rows between fuse
+        # and encode, and the encode reads the memory's rows.  Absent: nothing is built and every launch is what it is without it
+        from .teacher_memory import MAX_ROWS, LabelMemory, memory_config
+        self.memory_config = memory_config(cfg["trainer"].get("teacher_memory"), self.config.min_score, self.threshold,
+                                           cfg["tester"].get("nms_iou"), self.dataset.max_objs)
+        self.memory = None
+        self.last_memory = None                      # (matched, created, missed, dropped, evicted, skipped) of the batch collected last
+        if self.memory_config is not None:
+            if views * self.topk > MAX_ROWS:
+                raise ValueError("trainer.teacher_memory: %d view(s) x tester.topk = %d exceed the %d rows per image the merge takes"
+                                 % (views, self.topk, MAX_ROWS))
+            if self.loader is None:
+                from .helpers.dataloader_helper import build_unlabelled_loader
+                self.loader = build_unlabelled_loader(cfg["dataset"])
+            m = self.memory_config
+            self.memory = LabelMemory(self.loader.dataset.idx_list, m.slots, m.momentum, m.iou, m.drop_below, self.device)
 
     # ------------------------------------------------------------------------------------------------ weights
     def bind_source(self, ema):
@@ -431,17 +447,29 @@ class Teacher:
                                                    info["canonical_scale"]))
         if self.device.type == "cuda":
             prep, geom, records = prep.pin_memory(), geom.pin_memory(), records.pin_memory()
+        memory = self.memory
+        frames = None if memory is None else memory.positions(info["img_id"])      # host lookup; pinned beside the records
 
         def after(rows, count, slot):
+            stats = None
+            if memory is not None:                                    # between fuse and encode: the encode reads the memory's rows
+                if slot is None:
+                    rows, count, stats = memory.merge_host(rows.contiguous(), count.to(torch.int32), frames)
+                else:
+                    rows, count, stats = memory.merge(rows, count, frames.to(self.device, non_blocking=True))
             if slot is None:                                          # the CPU device: the host function
                 out = encode_targets_host(rows.numpy(), count.numpy(), records.numpy(), self.settings)
                 out = {k: torch.from_numpy(v) for k, v in out.items()}
-                return {"targets": out, "mask_2d": out["mask_2d"], "label_weight": out["label_weight"], "n_ignore": out["n_ignore"]}
+                host = {"targets": out, "mask_2d": out["mask_2d"], "label_weight": out["label_weight"], "n_ignore": out["n_ignore"]}
+                return host if stats is None else dict(host, memory=stats)
             out = encode_targets(rows, count, records.to(self.device, non_blocking=True), self.settings._replace(cls_mean_size=self._cms))
             host = {}
             for k in ("mask_2d", "label_weight", "n_ignore"):
                 host[k] = slot.pinned("teacher_" + k, out[k])
                 host[k].copy_(out[k], non_blocking=True)
+            if stats is not None:
+                host["memory"] = slot.pinned("teacher_memory", stats)
+                host["memory"].copy_(stats, non_blocking=True)
             return dict(host, targets=out)
         if self.device.type == "cuda":               # one upload: the engine's prepare now and collect()'s later read this copy
             canvas = canvas.to(self.device, non_blocking=True)
@@ -468,7 +496,9 @@ class Teacher:
         attach_host_weight(out["label_weight"], extra["label_weight"])
         attach_host_any(out["ignore_mask"], bool(np.asarray(extra["n_ignore"]).sum() > 0))
         self.last_counts = (int(np.count_nonzero(extra["mask_2d"])), int(np.asarray(extra["n_ignore"]).sum()))
-        self.last_rows = (done.rows, done.count)     # the (fused) rows the targets were encoded from, host copies
+        self.last_rows = (done.rows, done.count)     # the (fused) rows of this pass, host copies (with the memory on: what was merged)
+        if self.memory is not None:
+            self.last_memory = tuple(int(v) for v in np.asarray(extra["memory"]).reshape(-1, 6).sum(0))
         images = prepare(canvas, info["prep"], self.device)
         return images, calibs.to(self.device, non_blocking=True), out, info
 
