@@ -19,4 +19,7 @@ def __getattr__(name):
     if name == "LabelMemory":               # the label memory of self-training (monosowa_amd/teacher_memory.py)
         from .teacher_memory import LabelMemory
         return LabelMemory
+    if name == "TemplateFitter":            # the template-pose search behind the first pseudo-labels (monosowa_amd/template_fit.py)
+        from .template_fit import TemplateFitter
+        return TemplateFitter
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -26,6 +26,8 @@ LIBS = {
     "libmonosowa_gemm.so": ("gemm_lt.cpp", ["-lhipblaslt"]),      # host code only: the hipBLASLt shim (include/monosowa_gemm.h)
     # bit-exact with the CPU loader (include/monosowa_image.h): numpy rounds every product and sum, so nothing may contract to an FMA
     "libmonosowa_image.so": ("image_prep.hip", ["-ffp-contract=off"]),
+    # the template-pose search (include/monosowa_fit.h): its float32 contract is kept by a pragma in the translation unit
+    "libmonosowa_fit.so": ("template_fit.hip", []),
 }
 
 FLAGS = ["-O3", "--offload-arch=" + ARCH, "-munsafe-fp-atomics", "-fPIC", "-shared", "-std=c++17",
