@@ -22,4 +22,7 @@ def __getattr__(name):
     if name == "TemplateFitter":            # the template-pose search behind the first pseudo-labels (monosowa_amd/template_fit.py)
         from .template_fit import TemplateFitter
         return TemplateFitter
+    if name in ("ObjectLifter", "LiftResult", "lift_config", "lift_host"):   # depth map and masks to object clouds (monosowa_amd/lift.py)
+        from . import lift
+        return getattr(lift, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

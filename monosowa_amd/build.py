@@ -28,6 +28,8 @@ LIBS = {
     "libmonosowa_image.so": ("image_prep.hip", ["-ffp-contract=off"]),
     # the template-pose search (include/monosowa_fit.h): its float32 contract is kept by a pragma in the translation unit
     "libmonosowa_fit.so": ("template_fit.hip", []),
+    # depth map and masks to object clouds (include/monosowa_lift.h): a double / float32 contract, kept by the same pragma
+    "libmonosowa_lift.so": ("object_lift.hip", []),
 }
 
 FLAGS = ["-O3", "--offload-arch=" + ARCH, "-munsafe-fp-atomics", "-fPIC", "-shared", "-std=c++17",
