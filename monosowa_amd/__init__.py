@@ -25,4 +25,7 @@ def __getattr__(name):
     if name in ("ObjectLifter", "LiftResult", "lift_config", "lift_host"):   # depth map and masks to object clouds (monosowa_amd/lift.py)
         from . import lift
         return getattr(lift, name)
+    if name in ("ObjectTracker", "TrackResult", "track_config", "track_host"):   # centres to tracks, moving flags, headings (monosowa_amd/track.py)
+        from . import track
+        return getattr(track, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

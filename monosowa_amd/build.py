@@ -30,6 +30,8 @@ LIBS = {
     "libmonosowa_fit.so": ("template_fit.hip", []),
     # depth map and masks to object clouds (include/monosowa_lift.h): a double / float32 contract, kept by the same pragma
     "libmonosowa_lift.so": ("object_lift.hip", []),
+    # centres and statuses to tracks, moving flags and headings (include/monosowa_track.h): a double contract, the same pragma
+    "libmonosowa_track.so": ("object_track.hip", []),
 }
 
 FLAGS = ["-O3", "--offload-arch=" + ARCH, "-munsafe-fp-atomics", "-fPIC", "-shared", "-std=c++17",

@@ -12,8 +12,8 @@ mask shrunk by ``binary_dilation`` of its complement, the points behind it, medi
 reference frame) and ``standing_concatenate_lidar_clever`` / ``moving_lidar_keep_ref`` (the best views of a track concatenated).
 Stated deviations: float32 points with double medians (the reference's points are float64); the circle and range tests compare squares;
 mask membership is read at the pixel itself; a track beyond ``max_points`` is thinned by even spacing, not ``np.random.choice``;
-products run left to right.  Tracking, ICP and the moving / standing decision stay with the caller: ``tracks`` and ``moving``.
-HDBSCAN and context-aware growing are refused with ``ValueError``.
+products run left to right.  ``tracks`` and ``moving`` come from the tracker (monosowa_amd/track.py: ``ObjectTracker.track(res)``, then
+``res.gather(*tr.gather_args())``) or from the caller; ICP stays with the caller.  HDBSCAN and context-aware growing are refused with ``ValueError``.
 """
 import collections
 import ctypes

@@ -1,8 +1,8 @@
 """Object clouds from depth maps and instance masks (monosowa_amd/lift.py), written as the per-frame ``.npz`` files that
 tools/fit_labels.py reads.
 
-    python tools/lift_clouds.py --depth DIR --masks DIR --calib FILE [--poses FILE] [--tracks FILE] [--config YAML] --out DIR
-                                [--device cpu|cuda] [--max-points 16384]
+    python tools/lift_clouds.py --depth DIR --masks DIR --calib FILE [--poses FILE] [--tracks FILE | --track] [--config YAML]
+                                --out DIR [--device cpu|cuda] [--max-points 16384]
 
 ``--depth``: one ``<frame number>.npy`` per frame, float [H, W], metric depth.  ``--masks``: the same names, ``.npy`` or ``.npz`` (key
 ``masks``), bool or uint8 [M_f, H, W]; frames may differ in M_f.  ``--calib``: ``P2`` as ``.npy`` [3, 4] or [F, 3, 4], or ``.npz``
@@ -14,7 +14,11 @@ where a row has fewer views, and optionally ``moving`` [B]) and ``--poses`` (``.
 reference frame, whose index is ``frames_creation.nscans_before``), the views of a track are gathered (the ten best of a standing
 track, the reference frame's of a moving one) and one file is written, for the reference frame; a track without an OK view there is
 left out, as the reference leaves out objects that are not visible in the labelled frame.  ``box2d`` is the bounding box of the
-object's mask in the frame the file belongs to.  ``--config``: a YAML file with the reference's sections."""
+object's mask in the frame the file belongs to.  ``--track`` (with ``--poses``, instead of ``--tracks``) finds the tracks itself
+(monosowa_amd/track.py): lift, track and gather run back to back on the device, and the one file holds the kept tracks' clouds, ``box2d``
+from each track's mask in the reference frame, ``moving`` and ``theta`` (the heading of a moving track, NaN: none); a kept track
+without a view in the reference frame (possible only with ``use_pseudo_lidar: false``) has no such mask and is left out.  ``--config``: a YAML
+file with the reference's sections."""
 import argparse
 import glob
 import os
@@ -82,11 +86,14 @@ def main(argv=None):
     ap.add_argument("--calib", required=True)
     ap.add_argument("--poses")
     ap.add_argument("--tracks")
+    ap.add_argument("--track", action="store_true")
     ap.add_argument("--config")
     ap.add_argument("--out", required=True)
     ap.add_argument("--device")
     ap.add_argument("--max-points", type=int, default=16384)
     args = ap.parse_args(argv)
+    if args.track and (args.tracks is not None or args.poses is None):
+        ap.error("--track needs --poses and excludes --tracks")
     from monosowa_amd.lift import ObjectLifter, OK
     cfg = None
     if args.config:
@@ -99,25 +106,40 @@ def main(argv=None):
     lifter = ObjectLifter(cfg, device=args.device, max_points=args.max_points)
     os.makedirs(args.out, exist_ok=True)
 
-    def write(f, clouds, boxes, moving):
+    def write(f, clouds, boxes, moving, theta=None):
         arrays = {"P2": P2[f], "img_size": np.array([W, H], dtype=np.float64), "box2d": np.asarray(boxes, dtype=np.float64).reshape(-1, 4),
                   "moving": np.asarray(moving, dtype=np.uint8)}
+        if theta is not None:
+            arrays["theta"] = np.asarray([np.nan if t is None else t for t in theta], dtype=np.float64)
         arrays.update({"points_%d" % k: c for k, c in enumerate(clouds)})
         np.savez(os.path.join(args.out, "%06d.npz" % numbers[f]), **arrays)
         print("%06d: %d objects, %d points" % (numbers[f], len(clouds), sum(len(c) for c in clouds)))
 
-    if args.tracks is None:
+    if args.tracks is None and not args.track:
         res = lifter.lift(depth, intrinsics, masks, mask_count).numpy()         # each frame in its own coordinates: no pose
         for f in range(F):
             ok = [m for m in range(M) if (res["status"][f, m] & 7) == OK]
             write(f, [res["points"][f, m, :res["counts"][f, m]] for m in ok], [mask_box(masks[f, m]) for m in ok], [0] * len(ok))
         return 0
-    with np.load(args.tracks, allow_pickle=False) as z:
-        tracks = np.asarray(z["tracks"], dtype=np.int32)
-        moving = np.asarray(z["moving"]).astype(bool) if "moving" in z.files else np.zeros(tracks.shape[0], dtype=bool)
     ref = lifter.config.ref_frame
     if not 0 <= ref < F:
         raise SystemExit("the reference frame, index %d (frames_creation.nscans_before), is not among the %d frames" % (ref, F))
+    if args.track:
+        from monosowa_amd.track import ObjectTracker
+        res = lifter.lift(depth, intrinsics, masks, mask_count, poses)
+        tr = ObjectTracker(cfg, device=args.device).track(res)
+        clouds, counts, _ = res.gather(*tr.gather_args())
+        kept, moving, theta = tr.objects()                                      # the one wait
+        clouds, counts, ref_mask = clouds.cpu().numpy(), counts.cpu().numpy(), tr.ref_mask[0].cpu().numpy()
+        # a kept track without a view in the reference frame (a hidden standing car, kept when use_pseudo_lidar is false) has no
+        # mask to take a box from: left out, as the --tracks path leaves out a track without an OK view there
+        rows = [(b, mv, th) for b, mv, th in zip(kept, moving, theta) if counts[b] > 0 and ref_mask[b] >= 0]
+        write(ref, [clouds[b, :counts[b]] for b, _, _ in rows], [mask_box(masks[ref, ref_mask[b]]) for b, _, _ in rows],
+              [int(mv) for _, mv, _ in rows], [th for _, _, th in rows])
+        return 0
+    with np.load(args.tracks, allow_pickle=False) as z:
+        tracks = np.asarray(z["tracks"], dtype=np.int32)
+        moving = np.asarray(z["moving"]).astype(bool) if "moving" in z.files else np.zeros(tracks.shape[0], dtype=bool)
     res = lifter.lift(depth, intrinsics, masks, mask_count, poses)
     clouds, counts, _ = res.gather(tracks, moving)
     clouds, counts, status = clouds.cpu().numpy(), counts.cpu().numpy(), res.status.cpu().numpy()
