@@ -639,27 +639,42 @@ COLSUM_LEVELS_ONE_LAUNCH = 1     # all levels by one launch pair (mono_colsum_le
 _LEVEL_PLANS = {}                # (B, S, bounds) -> (ctypes int array, partial rows)
 
 
+def _level_bounds_checked(bounds, S):
+    """Raises for a level outside [0, S) or without rows: the per-level launches below address rows [a, b) of every batch as given."""
+    if not len(bounds) or any(not 0 <= a < b <= S for a, b in bounds):
+        raise RuntimeError("colsum_levels: unusable bounds %s for %d rows per batch" % (list(bounds), S))
+
+
 def colsum_levels(g3, bounds, with_total=False):
-    """Per-level column sums of a [B, S, C] tensor (contiguous, C <= 512): rows [a, b) of every batch for each (a, b)
-    in ``bounds`` -> [len(bounds), C].  ``with_total``: -> (the same, their sum over the levels [C]) -- from the same launch pair."""
+    """Per-level column sums of a [B, S, C] tensor: rows [a, b) of every batch for each (a, b) in ``bounds`` -> [len(bounds), C].
+    ``with_total``: -> (the same, their sum over the levels [C]) -- from the same launch pair.  HIP kernels for a contiguous,
+    16-byte aligned float32 GPU tensor with C % 4 == 0 and C <= 512, torch otherwise; RuntimeError for bounds outside [0, S]."""
     B, S, C = g3.shape
     L = len(bounds)
+    if not (g3.is_cuda and g3.dtype == torch.float32 and C % 4 == 0 and 0 < C <= 512 and B > 0 and g3.is_contiguous()
+            and g3.data_ptr() % 16 == 0):
+        _level_bounds_checked(bounds, S)
+        out = torch.stack([g3[:, a:b].sum((0, 1)) for a, b in bounds])
+        return (out, out.sum(0)) if with_total else out
     out = torch.empty((L + (1 if with_total else 0), C), dtype=torch.float32, device=g3.device)
     lib = load()
-    if COLSUM_LEVELS_ONE_LAUNCH and L <= 8 and C % 4 == 0 and C <= 512:
+    if COLSUM_LEVELS_ONE_LAUNCH and L <= 8:
         key = (B, S, tuple(tuple(ab) for ab in bounds))
         plan = _LEVEL_PLANS.get(key)
         if plan is None:
+            _level_bounds_checked(bounds, S)
             arr = (ctypes.c_int * (2 * L))(*[int(v) for ab in bounds for v in ab])
             plan = _LEVEL_PLANS[key] = (arr, lib.mono_colsum_levels_blocks(B, S, L, arr))
         arr, blocks = plan
-        if blocks > 0:
-            partials = torch.empty(blocks * C, dtype=torch.float32, device=g3.device)
-            with on_device(g3.device):
-                code = lib.mono_colsum_levels_f32(g3.data_ptr(), out.data_ptr(), partials.data_ptr(), B, S, C, L, arr, int(with_total), raw_stream())
-            if code:
-                raise RuntimeError("mono_colsum_levels_f32 failed with code %d" % code)
-            return (out[:L], out[L]) if with_total else out
+        if blocks <= 0:
+            raise RuntimeError("mono_colsum_levels_blocks refused bounds %s" % (list(bounds),))
+        partials = torch.empty(blocks * C, dtype=torch.float32, device=g3.device)
+        with on_device(g3.device):
+            code = lib.mono_colsum_levels_f32(g3.data_ptr(), out.data_ptr(), partials.data_ptr(), B, S, C, L, arr, int(with_total), raw_stream())
+        if code:
+            raise RuntimeError("mono_colsum_levels_f32 failed with code %d" % code)
+        return (out[:L], out[L]) if with_total else out
+    _level_bounds_checked(bounds, S)
     with on_device(g3.device):
         st = raw_stream()
         for i, (a, b) in enumerate(bounds):

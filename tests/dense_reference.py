@@ -294,3 +294,200 @@ def wgrad_coverage(split_lists):
 
 WGRAD_REQUIRED = ({"stages=%d" % n for n in range(9)} | {"chain=1", "chain=2", "chain=3"} | {"tail=0", "tail=1", "tail=2", "tail=15"}
                   | {"empty trailing split", "tail-only split"})
+
+
+# ---- the column-sum family of csrc/pointwise.hip (tests/test_column_sums_gpu.py) ---------------------------------------------------
+def colsum_operands(rows, C, seed=0, device="cpu"):
+    """g [rows, C] in [-3, 3]: every partial sum of a column, in any order and over any split, stays below 3 rows < 2^24."""
+    bound = MAT_MAX * rows
+    assert bound < EXACT_LIMIT, "operands are not exact in float32: bound %g >= 2^24" % bound
+    return dict(g=ints((rows, C), -MAT_MAX, MAT_MAX, _gen(seed, device), device), bound=bound)
+
+
+def colsum_batched_operands(B, S, C, seed=0, device="cpu"):
+    """g [B, S, C] in [-3, 3] for the strided and per-level sums.  The bound 3 * 8 * B * S also covers the sum over up to eight levels
+    that overlap (``with_total`` adds a row once per level that holds it)."""
+    bound = MAT_MAX * 8 * B * S
+    assert bound < EXACT_LIMIT, "operands are not exact in float32: bound %g >= 2^24" % bound
+    return dict(g=ints((B, S, C), -MAT_MAX, MAT_MAX, _gen(seed, device), device), bound=bound)
+
+
+def slices_operands(n, C, seed=0, device="cpu"):
+    """x [n, C] in [-3, 3], a stack of n slices: |sums| <= 3 n."""
+    bound = MAT_MAX * n
+    assert bound < EXACT_LIMIT, "operands are not exact in float32: bound %g >= 2^24" % bound
+    return dict(x=ints((n, C), -MAT_MAX, MAT_MAX, _gen(seed, device), device), bound=bound)
+
+
+def relu_dropout_colsum_operands(rows, seed=0, device="cpu"):
+    """gy [rows, 256] in [-3, 3], y [rows, 256] in [-8, 8] (zeros and negatives: the mask), for a scale of 1 or 2: |sums| <= 6 rows."""
+    bound = 2 * MAT_MAX * rows
+    assert bound < EXACT_LIMIT, "operands are not exact in float32: bound %g >= 2^24" % bound
+    g = _gen(seed, device)
+    return dict(gy=ints((rows, 256), -MAT_MAX, MAT_MAX, g, device), y=ints((rows, 256), -VEC_MAX, VEC_MAX, g, device), bound=bound)
+
+
+# The launchers' planning arithmetic restated (used to ASSERT what a case list reaches, and compared with the library's own planner
+# functions on the GPU box; never the expected value of a result).
+def reduce_plan(rows):
+    """(grid, rows_per_block) of mono_colsum_f32 / mono_colsum_strided_f32: mono_reduce_blocks doubles 64-row workgroups until at most
+    1024 are left; the launcher then rounds ceil(rows / grid) up to a multiple of 64."""
+    rpb = 64
+    while -(-rows // rpb) > 1024:
+        rpb *= 2
+    grid = -(-rows // rpb)
+    return grid, (-(-rows // grid) + 63) // 64 * 64
+
+
+def colsum_any_plan(rows):
+    """(grid, rows_per_block) of mono_colsum_any_f32: 128-row workgroups, 1 <= grid <= 512, rows_per_block = ceil(rows / grid)."""
+    grid = min(max(-(-rows // 128), 1), 512)
+    return grid, -(-rows // grid)
+
+
+def colsum_levels_plan(batch, S, bounds):
+    """[(grid, rows_per_block)] per level of mono_colsum_levels_f32, or None where mono_colsum_levels_blocks returns 0."""
+    if batch <= 0 or not 0 < len(bounds) <= 8:
+        return None
+    if any(a < 0 or b <= a or b > S for a, b in bounds):
+        return None
+    return [reduce_plan(batch * (b - a)) for a, b in bounds]
+
+
+def _vector_tags(tags, kind, grid, rpb, total, C):
+    """Tags of one colsum_kernel / colsum_levels_kernel grid over ``total`` rows and of the fold over its ``grid`` partial rows."""
+    last = total - (grid - 1) * rpb
+    assert 0 < last <= rpb
+    tags.update({"grid=%d" % grid if grid <= 2 else "grid>2", "rpb=%d" % rpb, "last%%4=%d" % (last % 4)})
+    if last == 1:
+        tags.add("last=1")
+    if last == rpb:
+        tags.add("last=full")
+    _fold_tags(tags, grid)
+    cv = C // 4
+    tags.add("JJ=%d,last=%d" % (1 if C <= 256 else 2 if C <= 512 else 4, (cv - 1) % 64 + 1))
+
+
+def _fold_tags(tags, n):
+    """partial_sum_kernel / partial_sum_levels_kernel: 16 waves take partial rows k, k + 16, ..."""
+    tags.add("n<16" if n < 16 else "n=16" if n == 16 else "n=1024" if n == 1024 else "n>16,%16!=0" if n % 16 else "n>16,%16=0")
+
+
+def _boundary_tags(tags, batch, rows_b, rpb):
+    """Rows k * rows_b, 0 < k < batch, of the virtual [batch * rows_b, C] matrix start a new batch.  The four waves of a workgroup take
+    rows r0 + 4 i + (0..3) together and r0 is a multiple of 64: a boundary that is no multiple of 4 lies inside such a step."""
+    for k in range(1, batch):
+        if (k * rows_b) % 4:
+            tags.add("batch boundary inside a four-row step")
+        if (k * rows_b) % rpb == 0:
+            tags.add("batch boundary on a workgroup edge")
+
+
+def colsum_coverage(cases):
+    """What a list of cases exercises, as a set of tags.  A case is a tuple led by the entry point's name:
+    ("colsum", rows, C), ("any", rows, C), ("strided", batch, rows, C, gap), ("levels", B, S, C, bounds, with_total),
+    ("slices", n, C), ("relu_dropout", rows, p)."""
+    tags = set()
+    for case in cases:
+        kind = case[0]
+        if kind == "colsum":
+            _, rows, C = case
+            _vector_tags(tags, kind, *reduce_plan(rows), rows, C)
+        elif kind == "strided":
+            _, batch, rows, C, gap = case
+            grid, rpb = reduce_plan(batch * rows)
+            _vector_tags(tags, kind, grid, rpb, batch * rows, C)
+            _boundary_tags(tags, batch, rows, rpb)
+            if gap:
+                tags.add("gap between batches")
+        elif kind == "levels":
+            _, B, S, C, bounds, with_total = case
+            plan = colsum_levels_plan(B, S, bounds)
+            assert plan is not None, case
+            for (a, b), (grid, rpb) in zip(bounds, plan):
+                _vector_tags(tags, kind, grid, rpb, B * (b - a), C)
+                _boundary_tags(tags, B, b - a, rpb)
+                if a:
+                    tags.add("level not at row 0")
+                if a % 2:
+                    tags.add("level at an odd row")
+                if b - a == 1:
+                    tags.add("level of one row")
+            tags.add("levels=%d" % len(bounds))
+            if with_total:
+                _fold_tags(tags, sum(g for g, _ in plan))
+        elif kind == "any":
+            _, rows, C = case
+            grid, rpb = colsum_any_plan(rows)
+            counts = [max(min(rows, (i + 1) * rpb) - i * rpb, 0) for i in range(grid)]
+            assert sum(counts) == rows
+            tags.update("scalar rem=%d" % (n % 4) for n in counts if n)
+            if counts[-1] == 0:
+                tags.add("scalar empty trailing workgroup")
+            if grid == 512 and -(-rows // 128) > 512:
+                tags.add("scalar 512-workgroup cap")
+            tags.add("scalar column passes=%d" % -(-C // 256))
+        elif kind == "slices":
+            _fold_tags(tags, case[1])
+        elif kind == "relu_dropout":
+            grid, _ = reduce_plan(case[1])
+            _fold_tags(tags, grid)
+            tags.add("relu_dropout wrap" if case[1] > 4 * grid else "relu_dropout one pass")       # rows beyond one grid pass of 4 waves
+        else:
+            raise ValueError(case)
+    return tags
+
+
+COLSUM_REQUIRED = ({"grid=1", "grid=2", "last=1", "last=full", "rpb=64", "rpb=128", "rpb=256"} | {"last%%4=%d" % k for k in range(4)}
+                   | {"n<16", "n=16", "n>16,%16!=0", "n=1024"}
+                   | {"JJ=%d,last=%d" % (jj, n) for jj in (1, 2, 4) for n in (1, 63, 64)}
+                   | {"scalar rem=%d" % k for k in range(4)} | {"scalar empty trailing workgroup", "scalar 512-workgroup cap"}
+                   | {"batch boundary inside a four-row step", "batch boundary on a workgroup edge", "level not at row 0",
+                      "level at an odd row", "level of one row", "levels=8", "gap between batches", "relu_dropout wrap"})
+
+
+# ---- the case lists: the smallest shapes that reach each path ----------------------------------------------------------------------
+COLSUM_ROWS = [1, 3, 4, 5, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025]
+COLSUM_WIDTHS = [4, 252, 256, 260, 508, 512]
+COLSUM_ABI_WIDTHS = [516, 1020, 1024]                       # colsum_kernel<4>: pointwise.colsum sends these to torch
+# 65535 / 65536 rows: 1024 workgroups of 64; 65537: 513 of 128; 131073: 513 of 256 -- narrow, and one wide case each (<= 135 MB)
+COLSUM_BIG = [(65535, 4), (65535, 260), (65536, 4), (65536, 512), (65537, 4), (65537, 516), (131073, 4), (131073, 256)]
+COLSUM_CASES = [("colsum", r, c) for r in COLSUM_ROWS for c in COLSUM_WIDTHS + COLSUM_ABI_WIDTHS] + [("colsum", r, c) for r, c in COLSUM_BIG]
+
+ANY_ROWS = [1, 2, 3, 4, 5, 127, 128, 129]
+ANY_ABI_WIDTHS = [1, 17, 81, 255, 257, 1023]
+ANY_BIG = [(65536, 1), (65536, 81), (65536, 257), (65537, 1), (65537, 17), (65537, 257)]       # <= 68 MB
+ANY_CASES = [("any", r, c) for r in ANY_ROWS for c in ANY_ABI_WIDTHS] + [("any", r, c) for r, c in ANY_BIG]
+ANY_WRAPPER_CASES = [("any", r, c) for r in (1, 5, 129) for c in (17, 81, 1023)] + [("any", 65537, 81)]       # through pointwise.colsum
+
+STRIDED_CASES = [("strided", b, r, c, gap) for b, r in ((1, 1), (3, 37), (2, 64), (5, 65), (16, 30)) for c in (4, 256, 260, 512)
+                 for gap in (0, 4, 8 * c)]
+
+
+def level_sets(S):
+    """name -> bounds for a [B, S, C] tensor.  "tiled": adjacent levels, a one-row level, odd starts; "gapped": rows between the levels
+    that belong to none (NaN in the test); "overlap": levels that share rows; "eight": the most one launch takes."""
+    if S == 5:
+        return {"tiled": [(0, 1), (1, 4), (4, 5)], "gapped": [(1, 2), (3, 5)], "overlap": [(0, 3), (1, 5), (2, 3)],
+                "eight": [(0, 1), (1, 2), (2, 3), (3, 4), (4, 5), (0, 5), (1, 4), (3, 5)]}
+    if S == 131:
+        # (3, 67): 64 rows, a batch boundary on a workgroup edge
+        return {"tiled": [(0, 3), (3, 67), (67, 68), (68, 131)], "gapped": [(1, 30), (33, 97), (99, 100), (101, 130)],
+                "overlap": [(0, 131), (5, 70), (64, 65)],
+                "eight": [(0, 1), (1, 2), (3, 20), (20, 37), (41, 105), (105, 110), (111, 128), (129, 131)]}
+    assert S == 777
+    # (77, 777): 4 x 700 rows = 44 workgroups; (13, 269): 256 rows, 16 workgroups for 4 batches
+    return {"tiled": [(0, 13), (13, 269), (269, 270), (270, 777)], "gapped": [(1, 2), (77, 777)], "overlap": [(0, 777), (5, 776), (333, 334)],
+            "eight": [(0, 64), (65, 66), (67, 195), (195, 300), (301, 302), (303, 700), (700, 701), (705, 777)]}
+
+
+LEVEL_CASES = [("levels", B, S, C, tuple(bounds), wt) for B, S in ((1, 5), (3, 131), (4, 777)) for C in (4, 256, 384, 512)
+               for name, bounds in level_sets(S).items() for wt in (0, 1)]
+NINE_LEVELS = {5: [(0, 1), (1, 2), (2, 3), (3, 4), (4, 5), (0, 5), (1, 4), (3, 5), (2, 5)],
+               131: [(0, 1), (1, 2), (3, 20), (20, 37), (41, 105), (105, 110), (111, 128), (129, 131), (7, 77)],
+               777: [(0, 64), (65, 66), (67, 195), (195, 300), (301, 302), (303, 700), (700, 701), (705, 777), (1, 777)]}
+
+SLICES_CASES = [("slices", n, c) for n in (1, 2, 15, 16, 17, 31, 32, 33, 64) for c in (4, 252, 256, 260, 65536)]
+RELU_DROPOUT_CASES = [("relu_dropout", r, p) for r in (1, 3, 4, 5, 255, 256, 257, 65536, 65537) for p in (0.0, 0.5)]
+
+COLSUM_ALL_CASES = COLSUM_CASES + ANY_CASES + ANY_WRAPPER_CASES + STRIDED_CASES + LEVEL_CASES + SLICES_CASES + RELU_DROPOUT_CASES

@@ -8,6 +8,8 @@ C2  linear_wgrad the same way, over a list of row counts ASSERTED to reach every
 C3  the pointwise family past one grid pass (8,388,608 + 1,024 floats), exact;
 C4  NaN / +Inf / -Inf through every ReLU site: the positions torch's composition gives, forward and backward;
 C5  GroupNorm at the edges the deterministic-parity tests leave out, against float64 with a per-output, cancellation-aware bound.
+C6  the column-sum family (colsum, colsum_any, colsum_strided, colsum_levels, sum_slices, relu_dropout_bwd_colsum): exact integers,
+    canaries and poisoned scratch at every planner edge -- in tests/test_column_sums_gpu.py.
 """
 import contextlib
 import functools

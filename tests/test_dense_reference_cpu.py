@@ -287,3 +287,99 @@ def test_wgrad_split_arithmetic():
     cov = R.wgrad_coverage([R.wgrad_splits(65, 8), R.wgrad_splits(2049, 32)])
     assert {"stages=0", "stages=1", "stages=3", "stages=5", "chain=1", "tail=1", "tail-only split", "empty trailing split"} <= cov
     assert "chain=3" not in cov and not R.WGRAD_REQUIRED <= cov
+
+
+# ---- the column-sum family: operands, planners and case lists of tests/test_column_sums_gpu.py -----------------------------------------
+def _sum_orders(g):
+    """Float32 column sums of [rows, C] in several orders: torch's own, the rows reversed, one row at a time backwards, and in 4-wave /
+    64-row / 16-way chunks added up afterwards (the kernels' shapes of split)."""
+    rows = g.shape[0]
+    yield g.sum(0)
+    yield g.flip(0).sum(0)
+    acc = torch.zeros(g.shape[1])
+    for r in range(min(rows, 300) - 1, -1, -1):
+        acc = acc + g[r]
+    yield acc + g[300:].sum(0)
+    for chunk in (4, 64):
+        parts = torch.stack([g[k:k + chunk].sum(0) for k in range(0, rows, chunk)])
+        yield parts.sum(0)
+        yield parts.flip(0).sum(0)
+    yield torch.stack([g[w::16].sum(0) for w in range(min(16, rows))]).sum(0)
+
+
+@pytest.mark.parametrize("rows", [1, 5, 1025, 65537])
+def test_colsum_operands_are_exact_in_float32_in_any_order(rows):
+    o = R.colsum_operands(rows, 12, seed=5)
+    assert o["bound"] == 3 * rows < R.EXACT_LIMIT and o["g"].abs().max() <= 3
+    want = o["g"].double().sum(0)
+    for got in _sum_orders(o["g"]):
+        _both(lambda: got, lambda: want)
+    if rows > 1000:
+        assert (o["g"] == 0).any() and (o["g"] < 0).any() and want.abs().max() > 0
+    with pytest.raises(AssertionError):
+        R.colsum_operands(1 << 23, 1)                                                  # 3 * 2^23 >= 2^24: refused before allocating
+
+
+def test_batched_slice_and_relu_dropout_operands_are_exact_in_float32():
+    o = R.colsum_batched_operands(4, 777, 8, seed=6)
+    assert o["bound"] == 3 * 8 * 4 * 777 < R.EXACT_LIMIT
+    g = o["g"]
+    for a, b in R.level_sets(777)["overlap"]:
+        want = g[:, a:b].double().sum((0, 1))
+        for got in _sum_orders(g[:, a:b].reshape(-1, 8)):
+            _both(lambda: got, lambda: want)
+    total = sum(g[:, a:b].sum((0, 1)) for a, b in R.NINE_LEVELS[777][:8])
+    _both(lambda: total, lambda: sum(g[:, a:b].double().sum((0, 1)) for a, b in R.NINE_LEVELS[777][:8]))
+    s = R.slices_operands(64, 260, seed=7)
+    assert s["bound"] == 192
+    for got in _sum_orders(s["x"]):
+        _both(lambda: got, lambda: s["x"].double().sum(0))
+    d = R.relu_dropout_colsum_operands(1025, seed=8)
+    assert d["bound"] == 6 * 1025 and (d["y"] == 0).any() and (d["y"] < 0).any() and (d["y"] > 0).any()
+    for scale in (1.0, 2.0):
+        gh = torch.where(d["y"] > 0, d["gy"] * scale, torch.zeros(()))
+        want = R.relu_backward64(d["y"], d["gy"]) * scale
+        _both(lambda: gh, lambda: want)
+        for got in _sum_orders(gh):
+            _both(lambda: got, lambda: want.sum(0))
+
+
+def test_colsum_planners():
+    assert R.reduce_plan(1) == (1, 64) and R.reduce_plan(64) == (1, 64) and R.reduce_plan(65) == (2, 64)
+    assert R.reduce_plan(65536) == (1024, 64) and R.reduce_plan(65537) == (513, 128)         # the two transitions
+    assert R.reduce_plan(131072) == (1024, 128) and R.reduce_plan(131073) == (513, 256)
+    assert R.reduce_plan(163200) == (638, 256)
+    for rows in (1, 63, 65, 1025, 65535, 65537, 131073, 163200):
+        grid, rpb = R.reduce_plan(rows)
+        assert grid <= 1024 and rpb % 64 == 0 and (grid - 1) * rpb < rows <= grid * rpb       # no empty workgroup, every row owned
+    assert R.colsum_any_plan(1) == (1, 1) and R.colsum_any_plan(128) == (1, 128) and R.colsum_any_plan(129) == (2, 65)
+    assert R.colsum_any_plan(65536) == (512, 128) and R.colsum_any_plan(65537) == (512, 129)
+    assert 512 * 129 - 65537 > 3 * 129 and 65537 - 508 * 129 == 5                           # three empty trailing workgroups, five rows in the last used one
+    assert R.colsum_levels_plan(4, 777, [(0, 13), (77, 777)]) == [(1, 64), (44, 64)]
+    for bad in ([(-1, 3)], [(3, 3)], [(4, 3)], [(0, 778)], [], [(0, 1)] * 9):
+        assert R.colsum_levels_plan(4, 777, bad) is None
+    assert R.colsum_levels_plan(0, 777, [(0, 1)]) is None
+
+
+def test_colsum_case_lists_reach_every_path():
+    cov = R.colsum_coverage(R.COLSUM_ALL_CASES)
+    assert R.COLSUM_REQUIRED <= cov, "not reached: %s" % sorted(R.COLSUM_REQUIRED - cov)
+    # the tags come from the right cases, and a list without them is seen to lack them
+    assert {"grid=2", "last=1", "last%4=1", "rpb=64", "JJ=1,last=1", "n<16"} == R.colsum_coverage([("colsum", 65, 4)])
+    assert "n=16" in R.colsum_coverage([("colsum", 1024, 4)]) and "n=1024" in R.colsum_coverage([("colsum", 65536, 4)])
+    assert {"rpb=128", "n>16,%16!=0", "last=1"} <= R.colsum_coverage([("colsum", 65537, 4)])
+    assert {"scalar empty trailing workgroup", "scalar 512-workgroup cap", "scalar rem=1"} <= R.colsum_coverage([("any", 65537, 17)])
+    assert "scalar empty trailing workgroup" not in R.colsum_coverage([("any", 65536, 17)])
+    assert "batch boundary on a workgroup edge" in R.colsum_coverage([("strided", 2, 64, 4, 0)])
+    assert "batch boundary inside a four-row step" in R.colsum_coverage([("strided", 5, 65, 4, 4)])
+    assert "batch boundary inside a four-row step" not in R.colsum_coverage([("strided", 2, 64, 4, 0)])
+    lv = R.colsum_coverage([("levels", 3, 131, 384, ((0, 3), (3, 67), (67, 68), (68, 131)), 1)])
+    assert {"level not at row 0", "level at an odd row", "level of one row", "batch boundary on a workgroup edge", "JJ=2,last=32"} <= lv
+    assert not R.COLSUM_REQUIRED <= R.colsum_coverage(R.COLSUM_CASES)
+    # what the issue lists is in the lists
+    assert {r for _, r, _ in R.COLSUM_CASES} == {1, 3, 4, 5, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 65535, 65536, 65537, 131073}
+    assert {c for _, _, c in R.COLSUM_CASES} == {4, 252, 256, 260, 508, 512, 516, 1020, 1024}
+    assert {r for _, r, _ in R.ANY_CASES} == {1, 2, 3, 4, 5, 127, 128, 129, 65536, 65537}
+    assert {c for _, _, c in R.ANY_CASES} == {1, 17, 81, 255, 257, 1023} and {c for _, _, c in R.ANY_WRAPPER_CASES} == {17, 81, 1023}
+    assert max(r * c * 4 for _, r, c in R.COLSUM_CASES + R.ANY_CASES) < 150e6
+    assert all(len(b) == 9 and R.colsum_levels_plan(2, S, b) is None and R.colsum_levels_plan(2, S, b[:8]) for S, b in R.NINE_LEVELS.items())
